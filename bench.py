@@ -20,9 +20,14 @@ N graphs at once, the reference's own job-level parallelism (src/evaluate.cpp:41
 contract; at N > 1 the ranks share one replicated graph and the line carries `exchanged_batches` / bytes all-gathered.
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel — the persistent
-worker kernel that processes the narrow batches, HIP-event timed on its own stream) and, at N = 1, `cpu_baseline` (the
-CPU oracle: strictly sequential on 1 core = the reference's execution model, plus `rounds_all_cores`) and `parity` (the
-device result of the last step against that sequential oracle run).
+worker kernel that processes the narrow batches, HIP-event timed on its own stream, in the timed steps themselves).
+
+A plain run only sets up, warms up, times the steps, writes the outputs (`--dump-outputs DIR`) and prints the line.
+`--full` adds what takes work of its own: at N = 1 `cpu_baseline` (the CPU oracle: strictly sequential on 1 core = the
+reference's execution model, plus `rounds_all_cores`) and `parity` (the device result of the last step against that
+sequential oracle run); at N > 1 `multi_gpu.wide_rounds`.
+
+`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy in float64 (see dump_outputs).
 """
 import argparse
 import json
@@ -64,6 +69,35 @@ def pin_to_gpu_numa_node(torch, index):
         return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(hg, out_dir):
+    """The marginalised graph (vertices, edges) and the per-blanket report of one marginalizeNoOptimize, as float64 .npy
+    files. The edge array is in key order (the library canonicalises it before handing it out); the blanket report is
+    sorted by root id and leaves out `round`, the streaming driver's doorbell number, which depends on timing. Where the
+    library reports "not defined" as a non-finite value — min_gap = +inf with fewer than two Chow-Liu weights to compare,
+    kld = NaN for a status that computes none — the file holds -1 (both are >= 0 otherwise), so every output is finite.
+    Beyond DUMP_BYTES in all (not the default workload: 30 MB) every array is cut to the same fixed, seeded sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids, poses = hg.vertices()
+    arrays = {"vertex_ids": ids, "vertex_poses": poses}
+    arrays.update({f"edge_{k}": v for k, v in hg.edges().items()})
+    bl = hg.blankets()
+    order = np.argsort(bl["root"], kind="stable")
+    arrays.update({f"blanket_{k}": bl[k][order] for k in ("root", "status", "info", "kld", "min_gap")})
+    for k in ("blanket_kld", "blanket_min_gap"):
+        arrays[k] = np.where(np.isfinite(arrays[k]), arrays[k], -1.0)
+    total = sum(a.size * 8 for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        if total > DUMP_BYTES:
+            a = a.reshape(-1)
+            a = a[np.sort(rng.choice(a.size, a.size * DUMP_BYTES // total, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -76,8 +110,11 @@ def main():
                     help="linearisation point (BASELINE config 5 is Global; local = the reference's default, LM on the blankets)")
     ap.add_argument("--config", choices=["synthetic", "parking"], default="synthetic",
                     help="synthetic = BASELINE config 5 (the headline metric); parking = config 4 (parking.g2o from tests/golden)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample-poses", type=int, default=0, help="0 = full workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline + parity check (N = 1) and multi_gpu.wide_rounds (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and parity")
+    ap.add_argument("--cpu-sample-poses", type=int, default=0, help="with --full: 0 = full workload")
     args = ap.parse_args()
 
     import torch
@@ -173,12 +210,14 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearse else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(replicas[-1], args.dump_outputs)
 
-    # N > 1 only, outside the timed region of `value`: the one-graph views, each guarded so that a failure costs a
-    # field, not the bench line.
+    # N > 1 with --full only, outside the timed region of `value`: the one-graph views, each guarded so that a failure
+    # costs a field, not the bench line.
     multi = {}
     extras_guard = None
-    if world > 1 and args.config == "synthetic":
+    if world > 1 and args.config == "synthetic" and args.full:
         # The extra run below drives RCCL inside the library across GPUs — a path no one-GPU box can rehearse. If it hangs,
         # the headline measured above must not be lost with it: after 5 minutes rank 0 prints the line without the extra
         # and every rank leaves.
@@ -317,7 +356,7 @@ def main():
         }
     if multi:
         out["multi_gpu"] = multi
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from tests import oracle_lib, util
         gs = g
         ws = which

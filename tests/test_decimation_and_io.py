@@ -1,7 +1,9 @@
 """CPU: decimation.h functions against a line-by-line Python restatement of src/decimation.cpp:11-49;
 native .g2o reader/writer against the Python parser."""
+import gzip
 import math
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -100,10 +102,11 @@ def test_glc_edge_with_general_information_is_folded_into_w(tmp_path):
     assert np.allclose(W2.T @ W2, W.T @ Om @ W, rtol=1e-13, atol=1e-13)
 
 
-def test_reference_dataset_loads_if_present():
-    path = "/root/reference/datasets/sphere.g2o"
-    if not os.path.exists(path):
-        pytest.skip("reference datasets exist only in the build container")
+def test_reference_dataset_loads_if_present(tmp_path):
+    """The reference's sphere.g2o, stored gzipped under tests/golden, through the Python and the native reader."""
+    path = str(tmp_path / "sphere.g2o")
+    with gzip.open(os.path.join(util.GOLDEN_DIR, "sphere.g2o.gz"), "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
     g = g2o_io.load_g2o(path)
     assert len(g["ids"]) == 2500 and len(g["edge_ij"]) == 4948 and g["pose_dim"] == 6
     hg = GraphWrapperHIP.load(path, ctx=oracle_lib.injected_context())
