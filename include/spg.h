@@ -319,6 +319,39 @@ typedef struct {
  * matrix is not PD. */
 int spg_graph_kullback_leibler(spg_graph *baseline, spg_graph *other, int32_t fixed_id, spg_kld_terms *out);
 
+/* ---- per-pose covariances from the sparse factor ---------------------------------------------------
+ * GraphWrapperISAM::covariance() (src/graph_wrapper_isam.cpp:259-262) asks iSAM for covariances().marginal(nodes):
+ * selected blocks of the inverse read from the sparse factor, where GraphWrapperG2O::covariance()
+ * (src/graph_wrapper_g2o.cpp:368-373, spg_graph_covariance) inverts the whole matrix. Here: the graph's information
+ * is factorised block-sparse over its own plan (nested dissection, no marginalised part), the selected inverse
+ * (Takahashi's recurrence) runs over every supernode and the requested blocks are read from it on the device. One
+ * route at every size: spg_ctx_set_linear_solver does not apply. Shared conventions: the gauge of spg_graph_covariance
+ * (fixed_id < 0: the smallest id), the fixed vertex's block is zero; ids, pairs and the fixed vertex are checked
+ * (SPG_EINVAL) before the backend (SPG_ESTATE without HIP); SPG_ENOTPD if an information matrix is not PD. */
+typedef struct {
+    double device_seconds;          /* HIP-event time: assembly + factorisation + selected inverse + extraction */
+    int32_t supernodes;             /* fronts of the assembly tree(s) */
+    double front_bytes;             /* bytes of fronts and of the selected inverse's Z blocks in HBM */
+    double factor_flops;            /* flops of the factorisation(s) */
+    double selinv_flops;            /* flops of the selected inverse's tile products (pads included) */
+} spg_cov_stats;
+/* The D x D marginal covariance of each listed vertex, row-major, in the order given; ids == NULL: every live vertex in
+ * ascending id order (n is ignored). Returns the number of doubles needed (count * D^2); writes only when
+ * out && cap >= that. */
+int64_t spg_graph_marginal_covariances(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                       spg_cov_stats *stats);
+/* For each of the n pairs (a, b) (pairs[2i], pairs[2i+1]), a != b vertices of one common live edge (binary, GLC or
+ * MULTI), the 2D x 2D block [[Saa, Sab], [Sba, Sbb]] row-major. A pair without a common edge is SPG_EINVAL (joint blocks
+ * of arbitrary pairs are not available). Returns n (2D)^2; writes only when out && cap >= that. */
+int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                    spg_cov_stats *stats);
+/* Per-vertex KLD: for every live vertex of other except the fixed one, kullbackLeiblerDivergence(diff, infox, maty,
+ * InformationInformation) (src/utils.cpp:70-97) with infox = Sx_ii^-1 (other's marginal), maty = Sy_ii^-1 (the
+ * baseline's) and diff as in spg_graph_kullback_leibler. Preconditions and error codes of spg_graph_kullback_leibler.
+ * Returns the count; writes ids (ascending) and kld when both are given and cap >= the count. */
+int spg_graph_marginal_kld(spg_graph *baseline, spg_graph *other, int32_t fixed_id, int32_t *ids, double *kld, int cap,
+                           spg_cov_stats *stats);
+
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the
  * smallest id), g2o's Levenberg-Marquardt for up to `iterations` iterations (the reference uses 50),
@@ -328,7 +361,8 @@ int spg_graph_kullback_leibler(spg_graph *baseline, spg_graph *other, int32_t fi
  * The estimates of the graph are updated in place. */
 enum { SPG_SOLVER_AUTO = 0, SPG_SOLVER_DENSE = 1, SPG_SOLVER_SPARSE = 2 };
 /* Which factorisation spg_graph_optimize / _optimize_fixed / _kullback_leibler of graphs of this context use.
- * AUTO (default): by size. DENSE beyond its capacity (32 k / 46 k variables) returns SPG_ECAPACITY. */
+ * AUTO (default): by size. DENSE beyond its capacity (32 k / 46 k variables) returns SPG_ECAPACITY. The covariance
+ * blocks (spg_graph_marginal_covariances / _joint_covariances / _marginal_kld) are always block-sparse. */
 int spg_ctx_set_linear_solver(spg_ctx *ctx, int solver);
 typedef struct {
     int32_t iterations, trials;          /* LM iterations run; linear systems solved */

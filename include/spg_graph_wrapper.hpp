@@ -390,6 +390,45 @@ public:
         if (terms) *terms = t;
         return t.kld;
     }
+    // GraphWrapperISAM::covariance (src/graph_wrapper_isam.cpp:259-262, covariances().marginal): the D x D marginal
+    // covariance of each vertex of `ids` (empty: every vertex, ascending id), read from the sparse factor's selected
+    // inverse; one d x d matrix per vertex, the fixed vertex's is zero. Not part of the reference's virtual set.
+    std::vector<MatrixXd> marginalCovariances(const std::vector<int> &ids = {}, int fixed_id = -1, spg_cov_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g);
+        std::vector<int32_t> w(ids.begin(), ids.end());
+        const int32_t *wp = ids.empty() ? nullptr : w.data();
+        int64_t need = spg_graph_marginal_covariances(_g, fixed_id, wp, (int)w.size(), nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(need, 0), "marginalCovariances");
+        std::vector<double> buf((size_t)std::max<int64_t>(need, 1));
+        check((int)std::min<int64_t>(spg_graph_marginal_covariances(_g, fixed_id, wp, (int)w.size(), buf.data(), need, stats), 0), "marginalCovariances");
+        return split_blocks(buf, need / (d * d), d);
+    }
+    // the 2D x 2D covariance [[Saa, Sab], [Sba, Sbb]] of each pair of vertices that share a live edge
+    std::vector<MatrixXd> jointCovariances(const std::vector<std::pair<int, int>> &pairs, int fixed_id = -1, spg_cov_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g);
+        std::vector<int32_t> p;
+        for (auto &q : pairs) { p.push_back(q.first); p.push_back(q.second); }
+        int64_t need = spg_graph_joint_covariances(_g, fixed_id, p.data(), (int)pairs.size(), nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(need, 0), "jointCovariances");
+        std::vector<double> buf((size_t)std::max<int64_t>(need, 1));
+        check((int)std::min<int64_t>(spg_graph_joint_covariances(_g, fixed_id, p.data(), (int)pairs.size(), buf.data(), need, stats), 0), "jointCovariances");
+        return split_blocks(buf, (int64_t)pairs.size(), 2 * d);
+    }
+    // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
+    // its marginal here, every vertex of `other` but the fixed one; ids ascending
+    std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {
+        GraphWrapperHIP *o = dynamic_cast<GraphWrapperHIP *>(other);
+        if (!o) throw std::runtime_error("marginalKullbackLeibler: the other graph is not a GraphWrapperHIP");
+        int n = spg_graph_marginal_kld(_g, o->_g, fixed_id, nullptr, nullptr, 0, nullptr);
+        check(std::min(n, 0), "marginalKullbackLeibler");
+        std::vector<int32_t> id((size_t)std::max(n, 1));
+        std::vector<double> kld((size_t)std::max(n, 1));
+        check(std::min(spg_graph_marginal_kld(_g, o->_g, fixed_id, id.data(), kld.data(), n, stats), 0), "marginalKullbackLeibler");
+        id.resize((size_t)n);
+        kld.resize((size_t)n);
+        if (ids) ids->assign(id.begin(), id.end());
+        return kld;
+    }
     // GraphWrapperG2O::chi2(other) (src/graph_wrapper_g2o.cpp:503-529): push; other's vertices take other's estimates
     // and are held fixed; optimise the rest; read chi2; pop
     double chi2(GraphWrapper *other) override {
@@ -486,6 +525,15 @@ private:
     GraphWrapperHIP(std::shared_ptr<Ctx> ctx, spg_graph *g, bool glc) : _ctx(std::move(ctx)), _g(g), _glc(glc) {}
     void check(int rc, const char *what) const {
         if (rc < 0) throw std::runtime_error(std::string(what) + " failed (" + std::to_string(rc) + "): " + ((_ctx && _ctx->h) ? spg_last_error(_ctx->h) : ""));
+    }
+    static std::vector<MatrixXd> split_blocks(const std::vector<double> &buf, int64_t n, int w) {
+        std::vector<MatrixXd> out;
+        for (int64_t i = 0; i < n; i++) {
+            MatrixXd m(w, w);
+            std::copy(buf.begin() + i * w * w, buf.begin() + (i + 1) * w * w, m.data());
+            out.push_back(std::move(m));
+        }
+        return out;
     }
     void snapshot(std::vector<int32_t> &ids, std::vector<double> &poses) const {
         int n = spg_graph_num_vertices(_g), ps = spg_graph_pose_dim(_g) == 3 ? 3 : 7;

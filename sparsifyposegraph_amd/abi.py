@@ -73,6 +73,15 @@ class KldTerms(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CovStats(C.Structure):
+    """spg_cov_stats (include/spg.h)"""
+    _fields_ = [("device_seconds", C.c_double), ("supernodes", C.c_int32), ("front_bytes", C.c_double),
+                ("factor_flops", C.c_double), ("selinv_flops", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OptimizeStats(C.Structure):
     """spg_optimize_stats (include/spg.h)"""
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),

@@ -3504,6 +3504,156 @@ extern "C" int spg_graph_kullback_leibler(spg_graph *base, spg_graph *other, int
     return 0;
 }
 
+// ================================================================================= covariance blocks (sparse factor)
+namespace {
+int live_index(const spg_graph *g, int32_t id) {
+    auto it = g->vidx.find(id);
+    return (it == g->vidx.end() || !g->valive[it->second]) ? -1 : it->second;
+}
+bool share_live_edge(const spg_graph *g, int32_t a, int32_t b) {
+    for (int32_t e : g->vr[a].adj) {
+        const GEdge &ge = g->edges[e];
+        if (!ge.alive) continue;
+        const int32_t *vs = edge_verts(g, ge);
+        for (int i = 0; i < ge.nv; i++) if (vs[i] == b) return true;
+    }
+    return false;
+}
+// every live vertex but the fixed one is a block, numbered by ascending id
+void stage_free_vertices(spg_graph *g, const std::vector<int32_t> &order, int fixed, DenseStage &st) {
+    st.pos.assign(g->vid.size(), -1);
+    int p = 0;
+    for (int32_t v : order) if (v != fixed) st.pos[v] = p++;
+    build_dense_stage(g, st);
+}
+void put_cov_stats(spg_cov_stats *st, double secs, const double *info) {
+    if (!st) return;
+    st->device_seconds = secs; st->supernodes = (int32_t)info[0]; st->front_bytes = info[1];
+    st->factor_flops = info[2]; st->selinv_flops = info[3];
+}
+// K vertex indices per request (-1 = the fixed vertex) -> (K D)^2 doubles per request
+int64_t cov_blocks(spg_graph *g, int fixed, const std::vector<int32_t> &order, int K, std::vector<int32_t> &req, double *out,
+                   spg_cov_stats *stats, const char *what) {
+    spg_ctx *ctx = g->ctx;
+    const int64_t n = (int64_t)req.size() / K, W = (int64_t)K * g->d, need = n * W * W;
+    if (!ctx->is_hip) {
+        snprintf(ctx->err, sizeof ctx->err, "%s needs the HIP backend", what);
+        return SPG_ESTATE;
+    }
+    for (int32_t &v : req) if (v == fixed) v = -1;
+    double secs = 0, info[4] = {0, 0, 0, 0};
+    if (n == 0 || order.size() < 2) {   // nothing but the fixed vertex: every block is zero
+        std::fill(out, out + need, 0.0);
+        put_cov_stats(stats, secs, info);
+        return need;
+    }
+    if (int rc = sync_device(g)) return rc;
+    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+    DenseStage st;
+    stage_free_vertices(g, order, fixed, st);
+    ctx->err[0] = 0;
+    int rc = spg::hip_sparse_cov_blocks(spg::hip_backend_stream(&ctx->be), st.in, K, req.data(), (int)n, out, &secs, info, ctx->err, sizeof ctx->err);
+    if (rc) return rc;
+    put_cov_stats(stats, secs, info);
+    return need;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_marginal_covariances(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                                  spg_cov_stats *stats) {
+    if (!g || g->active || (ids && n < 0)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_marginal_covariances: the fixed vertex is not in the graph");
+    std::vector<int32_t> req;
+    if (!ids) req = order;
+    else {
+        req.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            req[i] = live_index(g, ids[i]);
+            if (req[i] < 0) {
+                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_marginal_covariances: vertex %d is not in the graph", (int)ids[i]);
+                return SPG_EINVAL;
+            }
+        }
+    }
+    const int64_t need = (int64_t)req.size() * g->d * g->d;
+    if (!out || cap < need) return need;
+    return cov_blocks(g, fixed, order, 1, req, out, stats, "spg_graph_marginal_covariances");
+}
+
+extern "C" int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                               spg_cov_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_covariances: the fixed vertex is not in the graph");
+    std::vector<int32_t> req((size_t)2 * n);
+    for (int i = 0; i < n; i++) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        const int va = live_index(g, a), vb = live_index(g, b);
+        const char *why = (va < 0 || vb < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same"
+                          : !share_live_edge(g, va, vb) ? "the vertices share no live edge" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
+            return SPG_EINVAL;
+        }
+        req[2 * i] = va;
+        req[2 * i + 1] = vb;
+    }
+    const int64_t W = 2 * g->d, need = (int64_t)n * W * W;
+    if (!out || cap < need) return need;
+    return cov_blocks(g, fixed, order, 2, req, out, stats, "spg_graph_joint_covariances");
+}
+
+extern "C" int spg_graph_marginal_kld(spg_graph *base, spg_graph *other, int32_t fixed_id, int32_t *ids, double *kld, int cap,
+                                      spg_cov_stats *stats) {
+    if (!base || !other || base->active || other->active) return SPG_EINVAL;
+    spg_ctx *ctx = base->ctx;
+    if (base->d != other->d) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: pose dimensions differ");
+    std::vector<int32_t> ob = live_vertices_by_id(base), oo = live_vertices_by_id(other);
+    const int fb = resolve_fixed(base, ob, fixed_id);
+    if (fb < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the baseline");
+    const int fo = resolve_fixed(other, oo, base->vid[fb]);
+    if (fo < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the sparsified graph");
+    std::vector<int32_t> vb, vo, out_ids;
+    for (int32_t v : oo) {
+        if (v == fo) continue;
+        const int u = live_index(base, other->vid[v]);
+        if (u < 0) {
+            snprintf(ctx->err, sizeof ctx->err, "spg_graph_marginal_kld: the sparsified graph holds vertex %d, which the baseline lacks", (int)other->vid[v]);
+            return SPG_EINVAL;
+        }
+        vb.push_back(u);
+        vo.push_back(v);
+        out_ids.push_back(other->vid[v]);
+    }
+    const int nk = (int)vo.size();
+    if (!ids || !kld || cap < nk) return nk;
+    if (!ctx->is_hip || !other->ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_marginal_kld needs the HIP backend");
+    if (spg::hip_backend_device(&ctx->be) != spg::hip_backend_device(&other->ctx->be))
+        return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: both graphs must live on the same device");
+    double secs = 0, info[4] = {0, 0, 0, 0};
+    if (nk > 0) {
+        if (int rc = sync_device(base)) return rc;
+        if (int rc = sync_device(other)) return rc;
+        if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+        if (other->ctx != ctx) if (int rc = other->ctx->be.synchronize(other->ctx->be.user)) return rc;
+        DenseStage sb, so;
+        stage_free_vertices(base, ob, fb, sb);
+        stage_free_vertices(other, oo, fo, so);
+        std::vector<int64_t> kvb, kvo;
+        for (int i = 0; i < nk; i++) { kvb.push_back(base->vpose[vb[i]]); kvo.push_back(other->vpose[vo[i]]); }
+        ctx->err[0] = 0;
+        int rc = spg::hip_sparse_marginal_kld(spg::hip_backend_stream(&ctx->be), sb.in, so.in, vb.data(), vo.data(), nk, kvb.data(), kvo.data(),
+                                              kld, &secs, info, ctx->err, sizeof ctx->err);
+        if (rc) return rc;
+    }
+    std::copy(out_ids.begin(), out_ids.end(), ids);
+    put_cov_stats(stats, secs, info);
+    return nk;
+}
+
 // ================================================================================= optimize() (8f.1)
 static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<int32_t> &fixed_vertices, spg_optimize_stats *out) {
     spg_ctx *ctx = g->ctx;

@@ -87,6 +87,15 @@ int hip_sparse_optimize(void *stream, const DenseGraphIn &in, int n, int iterati
 int hip_sparse_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const uint8_t *is_marg_vertex,
                    const int32_t *kept_b, const int32_t *kept_o, int nk, const int64_t *kept_vpo_base, const int64_t *kept_vpo_other,
                    double *terms, double *seconds, double *info, char *err, size_t errlen);
+// Covariance blocks from the selected inverse over the graph's own plan (spg_sparse.inc). in.pos >= 0: the free
+// vertices. req: n requests of K (1 or 2) vertex indices, -1 = the fixed vertex; out (host): n (K D)^2 doubles, row-major.
+// info[4] += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops; *seconds += device time.
+int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, double *seconds, double *info,
+                          char *err, size_t errlen);
+// Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
+// one after the other), diff as in the global KLD.
+int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,
+                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, double *seconds, double *info, char *err, size_t errlen);
 
 // Interior-point NFR (spg_nfr_ip.hip): blankets of the Dense / Subgraph patterns without a closed form, one workgroup
 // each, everything in a per-blanket slice of a global workspace.

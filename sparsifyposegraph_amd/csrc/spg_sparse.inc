@@ -21,6 +21,8 @@
 // supernodes' diagonals, and trace(Lambda_y^-1 Lambda_x) from the selected inverse (Takahashi recurrence, top-down
 // over the kept fronts: Sigma_BB gathered from the parent, Y = L_BS L_SS^-1, Sigma_SB = -Y^T Sigma_BB,
 // Sigma_SS = L_SS^-T L_SS^-1 - Sigma_SB Y) contracted with the sparsified graph's Hessian blocks edge by edge.
+// Per-pose covariances run the same recurrence over every supernode of the graph's own plan and read the requested
+// blocks out of the fronts (sp_sigma_blocks_kernel; per-vertex marginal KLD: sp_marginal_kld_kernel).
 #include <cstdlib>
 #include <memory>
 
@@ -381,6 +383,88 @@ struct TraceSink {
     }
 };
 
+// Covariance blocks out of the selected inverse held in the fronts. Request i names K vertices by their positions
+// (D * elimination position; -1 = the fixed vertex, whose rows and columns are zero) and gets the (K D) x (K D) block
+// [Sigma(v_a, v_b)]_ab row-major at out + i (K D)^2. One wavefront per request; each D x D sub-block is read through
+// FrontSink::locate with pos(u) <= pos(v) (Sigma_SB is stored transposed; the lower-left block of a front still holds Y
+// and is never read), the upper sub-blocks by symmetry. Only real rows and columns are addressed, never the pads.
+// A sub-block outside the fronts sets bad = 2 and reads as zero.
+template <int D, int K>
+__global__ __launch_bounds__(64) void sp_sigma_blocks_kernel(FrontSink fs, const int32_t *req, int n, double *out) {
+    constexpr int W = K * D;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const int32_t *p = req + (long long)i * K;
+    double *o = out + (long long)i * W * W;
+    for (int e = lane; e < W * W; e += 64) {
+        const int a = e / W, b = e - a * W, ka = a / D, kb = b / D, r = a - ka * D, c = b - kb * D;
+        const int pa = p[ka], pb = p[kb];
+        double v = 0.0;
+        if (pa >= 0 && pb >= 0) {
+            const bool lower = pa >= pb;
+            const int pv = lower ? pa : pb, pu = lower ? pb : pa, rr = lower ? r : c, cc = lower ? c : r;
+            int ld; bool tr;
+            const double *blk = fs.locate(pv, pu, ld, tr, true);
+            if (blk) v = tr ? blk[(long long)cc * ld + rr] : blk[(long long)rr * ld + cc];
+        }
+        o[e] = v;
+    }
+}
+
+// Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
+// (src/utils.cpp:70-97) = 0.5 (tr(Sx^-1 Sy) + diff^T Sx^-1 diff + log det Sx - log det Sy - D), through the Cholesky
+// factors Sx = Lx Lx^T, Sy = Ly Ly^T: tr = || Lx^-1 Ly ||_F^2, Mahalanobis = || Lx^-1 diff ||^2. One lane per vertex,
+// fp64 in registers. bad[0] / bad[1]: Sy / Sx not positive definite.
+template <int D>
+__global__ __launch_bounds__(64) void sp_marginal_kld_kernel(const double *sx, const double *sy, const double *diff, int n, double *kld, int *bad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double Lx[D][D], Ly[D][D];
+#pragma unroll
+    for (int r = 0; r < D; r++)
+#pragma unroll
+        for (int c = 0; c < D; c++) { Lx[r][c] = sx[(long long)i * D * D + r * D + c]; Ly[r][c] = sy[(long long)i * D * D + r * D + c]; }
+    bool okx = true, oky = true;
+    double ldx = 0, ldy = 0;
+#pragma unroll
+    for (int j = 0; j < D; j++) {
+#pragma unroll
+        for (int k = 0; k < j; k++) { Lx[j][j] -= Lx[j][k] * Lx[j][k]; Ly[j][j] -= Ly[j][k] * Ly[j][k]; }
+        okx = okx && Lx[j][j] > 0.0 && isfinite(Lx[j][j]);
+        oky = oky && Ly[j][j] > 0.0 && isfinite(Ly[j][j]);
+        Lx[j][j] = sqrt(Lx[j][j]);
+        Ly[j][j] = sqrt(Ly[j][j]);
+        ldx += log(Lx[j][j]);
+        ldy += log(Ly[j][j]);
+#pragma unroll
+        for (int r = j + 1; r < D; r++) {
+#pragma unroll
+            for (int k = 0; k < j; k++) { Lx[r][j] -= Lx[r][k] * Lx[j][k]; Ly[r][j] -= Ly[r][k] * Ly[j][k]; }
+            Lx[r][j] /= Lx[j][j];
+            Ly[r][j] /= Ly[j][j];
+        }
+    }
+    if (!okx || !oky) {
+        if (!oky) bad[0] = 1;
+        if (!okx) bad[1] = 1;
+        kld[i] = __builtin_nan("");
+        return;
+    }
+    double tr = 0, mahal = 0, z[D];
+#pragma unroll
+    for (int c = 0; c <= D; c++) {     // columns of Ly, then diff
+#pragma unroll
+        for (int r = 0; r < D; r++) {
+            double s = (c == D) ? diff[(long long)i * D + r] : (r >= c ? Ly[r][c] : 0.0);
+#pragma unroll
+            for (int k = 0; k < r; k++) s -= Lx[r][k] * z[k];
+            z[r] = s / Lx[r][r];
+            if (c == D) mahal += z[r] * z[r]; else tr += z[r] * z[r];
+        }
+    }
+    kld[i] = 0.5 * (tr + mahal + 2 * ldx - 2 * ldy - D);
+}
+
 // ------------------------------------------------------------------------------------------ host side
 struct SpStep {
     enum Kind { GEMM, DIAG, EXTADD, GATHER } kind;
@@ -397,6 +481,7 @@ struct SparseSolver {
     std::vector<int64_t> zoff;
     int64_t zpool_len = 0;
     int n_kept_sn = 0;
+    double selinv_flops = 0;   // of the selected inverse's tile products as executed (pads included)
     const int64_t *d_zoff = nullptr;
     size_t bytes = 0;
 
@@ -531,6 +616,7 @@ struct SparseSolver {
             gemm(fact_steps, b0);
         }
         if (!with_selinv) return;
+        const size_t sel_begin = h_gemm.size();
         // ---- selected inverse over the kept supernodes, top-down
         for (int l = P.nlevels - 1; l >= 0; l--) {
             std::vector<int> sn;
@@ -608,6 +694,7 @@ struct SparseSolver {
             }
             gemm(sel_steps, b0);
         }
+        for (size_t k = sel_begin; k < h_gemm.size(); k++) selinv_flops += 2.0 * 64 * 64 * 64 * h_gemm[k].nk;
     }
 
     int upload_items(char *err, size_t errlen) {
@@ -654,6 +741,14 @@ struct SparseSolver {
         FrontSink sink{dev, bad ? bad : (int *)own_bad.p};
         if (D == 6) launch_assemble_into<6>(gb, sink, s, b);
         else launch_assemble_into<3>(gb, sink, s, b);
+        return 0;
+    }
+    // fronts <- the partial factorisations of the staged graph's H (no shift): the step the global KLD and the
+    // covariance blocks share
+    int factorise(hipStream_t s, const GraphBufs &gb, int *bad) {
+        if (int rc = assemble(s, gb, nullptr, bad)) return rc;
+        shift(s, 0.0, nullptr, 0);
+        factor(s, bad);
         return 0;
     }
     // pivot diagonals += lambda, pads = 1; scal[slot] <- max |diag| before the shift (when scal != nullptr)
@@ -755,6 +850,29 @@ int sparse_leaf(int D) {
     return v > 0 ? v : (D == 6 ? 32 : 64);
 }
 
+// Plan of a staged graph: blocks = its free vertices numbered by ascending in.pos, is_marg_vertex (per vertex, or null)
+// = the blocks to eliminate first; pos[v] = D * elimination position of vertex v, -1 for the others.
+void plan_of(const spg::DenseGraphIn &in, const uint8_t *is_marg_vertex, spg::sparse::Plan &plan, std::vector<int32_t> &pos) {
+    std::vector<int32_t> blk((size_t)in.nv, -1);
+    int nb = 0;
+    {
+        std::vector<std::pair<int32_t, int32_t>> order;
+        for (int v = 0; v < in.nv; v++) if (in.pos[v] >= 0) order.push_back({in.pos[v], v});
+        std::sort(order.begin(), order.end());
+        for (auto &p : order) blk[p.second] = nb++;
+    }
+    std::vector<uint8_t> im;
+    if (is_marg_vertex) {
+        im.assign((size_t)nb, 0);
+        for (int v = 0; v < in.nv; v++) if (blk[v] >= 0 && is_marg_vertex[v]) im[blk[v]] = 1;
+    }
+    spg::sparse::BlockGraph bg;
+    block_graph_of(in, blk, nb, bg);
+    spg::sparse::build_plan(bg, in.D, is_marg_vertex ? im.data() : nullptr, sparse_leaf(in.D), plan);
+    pos.assign((size_t)in.nv, -1);
+    for (int v = 0; v < in.nv; v++) if (blk[v] >= 0) pos[v] = in.D * plan.iperm[blk[v]];
+}
+
 // Sparse linear algebra for LM: the fronts are re-assembled for every trial (the estimates of a trial are those
 // of its iteration), shifted by lambda, factorised, and the right-hand side is solved in place.
 struct SparseLM : LMLinear {
@@ -838,29 +956,10 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &
     int rc = 0;
     const int D = base_.D;
     // ---- plans
-    std::vector<int32_t> blk_b((size_t)base_.nv, -1), blk_o((size_t)other_.nv, -1);
-    int nb_b = 0, nb_o = 0;
-    {
-        std::vector<std::pair<int32_t, int32_t>> order;
-        for (int v = 0; v < base_.nv; v++) if (base_.pos[v] >= 0) order.push_back({base_.pos[v], v});
-        std::sort(order.begin(), order.end());
-        for (auto &p : order) blk_b[p.second] = nb_b++;
-        order.clear();
-        for (int v = 0; v < other_.nv; v++) if (other_.pos[v] >= 0) order.push_back({other_.pos[v], v});
-        std::sort(order.begin(), order.end());
-        for (auto &p : order) blk_o[p.second] = nb_o++;
-    }
-    std::vector<uint8_t> im((size_t)nb_b, 0);
-    for (int v = 0; v < base_.nv; v++) if (blk_b[v] >= 0 && is_marg_vertex[v]) im[blk_b[v]] = 1;
-    sparse::BlockGraph gb_, go_;
-    block_graph_of(base_, blk_b, nb_b, gb_);
-    block_graph_of(other_, blk_o, nb_o, go_);
     sparse::Plan pb, po;
-    sparse::build_plan(gb_, D, im.data(), sparse_leaf(D), pb);
-    sparse::build_plan(go_, D, nullptr, sparse_leaf(D), po);
-    std::vector<int32_t> pos_b((size_t)base_.nv, -1), pos_o((size_t)other_.nv, -1), pos_ob((size_t)other_.nv, -1);
-    for (int v = 0; v < base_.nv; v++) if (blk_b[v] >= 0) pos_b[v] = D * pb.iperm[blk_b[v]];
-    for (int v = 0; v < other_.nv; v++) if (blk_o[v] >= 0) pos_o[v] = D * po.iperm[blk_o[v]];
+    std::vector<int32_t> pos_b, pos_o, pos_ob((size_t)other_.nv, -1);
+    plan_of(base_, is_marg_vertex, pb, pos_b);
+    plan_of(other_, nullptr, po, pos_o);
     for (int i = 0; i < nk; i++) pos_ob[kept_o[i]] = pos_b[kept_b[i]];    // other's vertices at the baseline's positions
     if (info) { info[0] = pb.nsn; info[1] = pb.nlevels; info[2] = (double)(pb.pool + po.pool) * 8; info[3] = pb.flops + po.flops; }
     const int n_marg_sn = pb.n_marg_sn;
@@ -896,18 +995,14 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &
         int *bad0 = (int *)bad.p, *bad1 = (int *)bad.p + 1;
         double *out = (double *)outb.p, *dk = (double *)diff.p, *dperm = (double *)diff.p + (size_t)std::max(nk, 1) * D;
         // sparsified graph: factor, log det, Mahalanobis term || L_x^T diff ||^2
-        if ((rc = so->assemble(s, gbo, nullptr, bad1))) goto done;
-        so->shift(s, 0.0, nullptr, 0);
-        so->factor(s, bad1);
+        if ((rc = so->factorise(s, gbo, bad1))) goto done;
         so->logdiag(s, 0, out, 1);
         if (D == 6) hipLaunchKernelGGL((pose_diff_kernel<6>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, dk);
         else hipLaunchKernelGGL((pose_diff_kernel<3>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, dk);
         hipLaunchKernelGGL(scatter_blocks_kernel, dim3((nk * D + 255) / 256), dim3(256), 0, s, (const double *)dk, (const int32_t *)dpos.p, nk, D, dperm);
         so->ltx_norm2(s, dperm, out, 3);
         // baseline: marginalised blocks first; log det of the marginal from the kept supernodes; selected inverse
-        if ((rc = sb->assemble(s, gbb, nullptr, bad0))) goto done;
-        sb->shift(s, 0.0, nullptr, 0);
-        sb->factor(s, bad0);
+        if ((rc = sb->factorise(s, gbb, bad0))) goto done;
         sb->logdiag(s, n_marg_sn, out, 2);
         if ((rc = sb->selected_inverse(s, bad0))) goto done;
         // trace(Sigma_kept Lambda_x): the sparsified graph's Hessian blocks against the selected inverse
@@ -936,6 +1031,141 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &
         terms[0] = 0.5 * (innerprod + mahal - logdetx - logdety - n_keep);
         terms[1] = innerprod; terms[2] = mahal; terms[3] = logdetx; terms[4] = logdety; terms[5] = n_keep;
         if (seconds) *seconds = 1e-3 * ms;
+    }
+done:
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+// Covariance blocks of a staged graph (in.pos >= 0: its free vertices, ascending = the block numbering) from the selected
+// inverse over its own plan: no marginalised part, so the item lists of the top-down recurrence cover every supernode
+// and the Z blocks take sum NP^2 over all of them. req: n requests of K vertex indices (-1 = zero rows and columns);
+// the blocks land in d_out (device, n (K D)^2 doubles). The fronts are released on return, before a caller factorises
+// a second graph. info[4] += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops;
+// *seconds += HIP-event time of assembly, factorisation, selected inverse and extraction.
+static int sigma_blocks(hipStream_t s, const DenseGraphIn &in_, int K, const int32_t *req, int n, double *d_out, double *seconds, double *info,
+                        char *err, size_t errlen) {
+    const int D = in_.D;
+    int rc = 0;
+    sparse::Plan plan;
+    std::vector<int32_t> pos;
+    plan_of(in_, nullptr, plan, pos);
+    std::vector<int32_t> rpos((size_t)n * K);
+    for (size_t i = 0; i < rpos.size(); i++) {
+        rpos[i] = req[i] < 0 ? -1 : pos[req[i]];
+        if (req[i] >= 0 && rpos[i] < 0) { snprintf(err, errlen, "covariance blocks: a requested vertex is not a variable"); return SPG_ESTATE; }
+    }
+    auto sp = std::make_unique<SparseSolver>();
+    const int nsn = plan.nsn;
+    const double fflops = plan.flops;
+    if ((rc = sp->init(std::move(plan), true, err, errlen))) return rc;
+    if (info) { info[0] += nsn; info[1] += (double)(sp->plan.pool + sp->zpool_len) * 8; info[2] += fflops; info[3] += sp->selinv_flops; }
+    DenseGraphIn in = in_;
+    in.pos = pos.data();
+    GraphBufs gb;
+    DevBuf bad, dreq;
+    int h_bad[2] = {0, 0};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    if ((rc = upload(dreq, rpos.data(), rpos.size(), s)) || (rc = stage_graph(in, gb, s))) {
+        snprintf(err, errlen, "staging the graph for the covariance blocks failed (%d)", rc);
+        goto done;
+    }
+    HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
+    HIPCHK(hipEventRecord(e0, s));
+    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); goto done; }
+    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); goto done; }
+    if (n > 0) {
+        const FrontSink fs{sp->dev, (int *)bad.p + 1};
+        const int32_t *rq = (const int32_t *)dreq.p;
+        if (D == 6 && K == 1) hipLaunchKernelGGL((sp_sigma_blocks_kernel<6, 1>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
+        else if (D == 6) hipLaunchKernelGGL((sp_sigma_blocks_kernel<6, 2>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
+        else if (K == 1) hipLaunchKernelGGL((sp_sigma_blocks_kernel<3, 1>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
+        else hipLaunchKernelGGL((sp_sigma_blocks_kernel<3, 2>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    if (seconds) *seconds += 1e-3 * ms;
+    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
+    if (h_bad[1]) { snprintf(err, errlen, "covariance blocks: a requested pair lies outside the fronts of the factorisation"); rc = SPG_ESTATE; goto done; }
+done:
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, double *seconds, double *info,
+                          char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int W = K * in.D;
+    const size_t len = (size_t)std::max(n, 1) * W * W;
+    int rc = 0;
+    DevBuf dout;
+    HIPCHK(hipMalloc(&dout.p, len * 8));
+    if ((rc = sigma_blocks(s, in, K, req, n, (double *)dout.p, seconds, info, err, errlen))) goto done;
+    if (n > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)n * W * W * 8, hipMemcpyDeviceToHost));
+done:
+    return rc;
+}
+
+int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,
+                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, double *seconds, double *info, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int D = base.D;
+    const size_t len = (size_t)std::max(nk, 1) * D * D;
+    int rc = 0, h_bad[2] = {0, 0};
+    DevBuf sy, sx, diff, dk, bad, pb, po;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    HIPCHK(hipMalloc(&sy.p, len * 8));
+    HIPCHK(hipMalloc(&sx.p, len * 8));
+    HIPCHK(hipMalloc(&diff.p, (size_t)std::max(nk, 1) * D * 8));
+    HIPCHK(hipMalloc(&dk.p, (size_t)std::max(nk, 1) * 8));
+    HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    // one graph after the other: the baseline's fronts are gone before the sparsified graph is factorised
+    if ((rc = sigma_blocks(s, base, 1, vb, nk, (double *)sy.p, seconds, info, err, errlen))) {
+        if (rc == SPG_ENOTPD) snprintf(err, errlen, "marginal KLD: the baseline information matrix is not positive definite");
+        goto done;
+    }
+    if ((rc = sigma_blocks(s, other, 1, vo, nk, (double *)sx.p, seconds, info, err, errlen))) {
+        if (rc == SPG_ENOTPD) snprintf(err, errlen, "marginal KLD: the sparsified information matrix is not positive definite");
+        goto done;
+    }
+    if ((rc = upload(pb, vpo_base, (size_t)nk, s)) || (rc = upload(po, vpo_other, (size_t)nk, s))) {
+        snprintf(err, errlen, "staging the pose offsets for the marginal KLD failed (%d)", rc);
+        goto done;
+    }
+    HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
+    HIPCHK(hipEventRecord(e0, s));
+    if (nk > 0) {
+        const dim3 g((nk + 63) / 64), b(64);
+        if (D == 6) {
+            hipLaunchKernelGGL((pose_diff_kernel<6>), g, b, 0, s, (const double *)base.dev_arena, (const int64_t *)pb.p, (const double *)other.dev_arena, (const int64_t *)po.p, nk, (double *)diff.p);
+            hipLaunchKernelGGL((sp_marginal_kld_kernel<6>), g, b, 0, s, (const double *)sx.p, (const double *)sy.p, (const double *)diff.p, nk, (double *)dk.p, (int *)bad.p);
+        } else {
+            hipLaunchKernelGGL((pose_diff_kernel<3>), g, b, 0, s, (const double *)base.dev_arena, (const int64_t *)pb.p, (const double *)other.dev_arena, (const int64_t *)po.p, nk, (double *)diff.p);
+            hipLaunchKernelGGL((sp_marginal_kld_kernel<3>), g, b, 0, s, (const double *)sx.p, (const double *)sy.p, (const double *)diff.p, nk, (double *)dk.p, (int *)bad.p);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (nk > 0) HIPCHK(hipMemcpyAsync(kld, dk.p, (size_t)nk * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    if (seconds) *seconds += 1e-3 * ms;
+    if (h_bad[0] || h_bad[1]) {
+        snprintf(err, errlen, "marginal KLD: a marginal covariance of the %s graph is not positive definite", h_bad[0] ? "baseline" : "sparsified");
+        rc = SPG_ENOTPD;
     }
 done:
     if (e0) (void)hipEventDestroy(e0);

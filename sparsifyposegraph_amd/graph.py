@@ -258,6 +258,51 @@ class GraphWrapperHIP:
         self.last_kld_terms = t.asdict()
         return t.kld
 
+    def marginalCovariances(self, ids=None, fixed_id=-1):
+        """GraphWrapperISAM::covariance (src/graph_wrapper_isam.cpp:259-262): the marginal covariance of each vertex,
+        read from the selected inverse of the sparse factor. ids=None: every vertex, ascending id. Returns
+        (ids, float64[n, D, D]); the fixed vertex's block is zero. Stats in `last_covariance_stats`."""
+        d, st = self.d, abi.CovStats()
+        if ids is None:
+            ids = self.vertices()[0]
+            ip = None
+        else:
+            ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+            ip = _p(ids, C.c_int32)
+        n = self.L.spg_graph_marginal_covariances(self.h, int(fixed_id), ip, len(ids), None, 0, None)
+        check(min(int(n), 0), self.ctx.h, "marginalCovariances")
+        out = np.zeros((int(n) // (d * d), d, d))
+        rc = self.L.spg_graph_marginal_covariances(self.h, int(fixed_id), ip, len(ids), _p(out, C.c_double), out.size, C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "marginalCovariances")
+        self.last_covariance_stats = st.asdict()
+        return np.asarray(ids, np.int32), out
+
+    def jointCovariances(self, pairs, fixed_id=-1):
+        """The 2D x 2D covariance [[Saa, Sab], [Sba, Sbb]] of each pair (a, b) of vertices that share a live edge, from
+        the selected inverse of the sparse factor. Returns float64[n, 2D, 2D]. Stats in `last_covariance_stats`."""
+        d, st = self.d, abi.CovStats()
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = self.L.spg_graph_joint_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), None, 0, None)
+        check(min(int(n), 0), self.ctx.h, "jointCovariances")
+        out = np.zeros((len(pr), 2 * d, 2 * d))
+        rc = self.L.spg_graph_joint_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), _p(out, C.c_double), out.size, C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "jointCovariances")
+        self.last_covariance_stats = st.asdict()
+        return out
+
+    def marginalKullbackLeibler(self, other, fixed_id=-1):
+        """Called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other`
+        against its marginal here, for every vertex of `other` but the fixed one. Returns (ids, kld), ascending ids.
+        Stats in `last_covariance_stats`."""
+        st = abi.CovStats()
+        n = self.L.spg_graph_marginal_kld(self.h, other.h, int(fixed_id), None, None, 0, None)
+        check(n, self.ctx.h, "marginalKullbackLeibler")
+        ids, kld = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
+        rc = self.L.spg_graph_marginal_kld(self.h, other.h, int(fixed_id), _p(ids, C.c_int32), _p(kld, C.c_double), n, C.byref(st))
+        check(rc, self.ctx.h, "marginalKullbackLeibler")
+        self.last_covariance_stats = st.asdict()
+        return ids[:n], kld[:n]
+
     # round-stepping form (multi-GPU driver in parallel.py)
     def begin(self, which, opts, rank, nranks):
         which = np.ascontiguousarray(which, np.int32)
