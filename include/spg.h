@@ -341,8 +341,8 @@ typedef struct {
 int64_t spg_graph_marginal_covariances(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
                                        spg_cov_stats *stats);
 /* For each of the n pairs (a, b) (pairs[2i], pairs[2i+1]), a != b vertices of one common live edge (binary, GLC or
- * MULTI), the 2D x 2D block [[Saa, Sab], [Sba, Sbb]] row-major. A pair without a common edge is SPG_EINVAL (joint blocks
- * of arbitrary pairs are not available). Returns n (2D)^2; writes only when out && cap >= that. */
+ * MULTI), the 2D x 2D block [[Saa, Sab], [Sba, Sbb]] row-major. A pair without a common edge is SPG_EINVAL (arbitrary
+ * pairs: spg_graph_pair_covariances). Returns n (2D)^2; writes only when out && cap >= that. */
 int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
                                     spg_cov_stats *stats);
 /* Per-vertex KLD: for every live vertex of other except the fixed one, kullbackLeiblerDivergence(diff, infox, maty,
@@ -351,6 +351,34 @@ int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_
  * Returns the count; writes ids (ascending) and kld when both are given and cap >= the count. */
 int spg_graph_marginal_kld(spg_graph *baseline, spg_graph *other, int32_t fixed_id, int32_t *ids, double *kld, int cap,
                            spg_cov_stats *stats);
+
+/* ---- covariance of arbitrary pose pairs and pose sets ------------------------------------------------
+ * Blocks outside the fronts (two vertices without a common live edge) are columns of Sigma = H^-1 solved through the
+ * fronts: Sigma[:, b] = L^-T L^-1 E_b with D right-hand sides per column vertex b, batched into panels of up to 512
+ * right-hand sides, the forward sweep over the fronts on b's path to the root only and the backward sweep over the
+ * paths to the requested rows only. One column serves every off-pattern partner of its vertex (greedy cover: one vertex
+ * against all others is one column). Diagonal and in-pattern blocks are read from the selected inverse as the calls
+ * above read them (bit for bit equal to spg_graph_marginal_covariances / _joint_covariances); the solved ones agree with
+ * them to rounding. Conventions of the calls above (gauge, zero fixed block, argument errors before the backend,
+ * SPG_ESTATE without HIP, SPG_ENOTPD); SPG_ECAPACITY if the panels of one batch do not fit in free HBM. */
+typedef struct {
+    spg_cov_stats cov;        /* as above; device_seconds covers the solves too */
+    int32_t columns;          /* vertices whose D columns of Sigma were solved for */
+    int32_t rhs_batches;      /* multi-RHS forward/backward sweeps run */
+    double solve_flops;       /* flops of the solve tile products as executed (pads included) */
+    double solve_seconds;     /* HIP-event time of the solves alone */
+} spg_cov_solve_stats;
+/* For each of the n pairs (a, b) (pairs[2i], pairs[2i+1]), two distinct live vertices, with or without a common edge:
+ * the 2D x 2D block [[Saa, Sab], [Sba, Sbb]], row-major, the layout of spg_graph_joint_covariances. Unknown ids and
+ * a == b are SPG_EINVAL. Returns n (2D)^2; writes only when out && cap >= that. */
+int64_t spg_graph_pair_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                   spg_cov_solve_stats *stats);
+/* iSAM's covariances().marginal(list) (src/graph_wrapper_isam.cpp:259-262): the (nD) x (nD) joint covariance of n
+ * distinct live vertices, in the order given, row-major. Each off-diagonal block is computed once and mirrored exactly;
+ * the diagonal blocks are those of spg_graph_marginal_covariances. Unknown or duplicate ids are SPG_EINVAL; n D above 46 000 (the bound of spg_graph_covariance) is
+ * SPG_ECAPACITY. Returns (nD)^2; writes only when out && cap >= that. */
+int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                            spg_cov_solve_stats *stats);
 
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the

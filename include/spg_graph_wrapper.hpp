@@ -414,6 +414,29 @@ public:
         check((int)std::min<int64_t>(spg_graph_joint_covariances(_g, fixed_id, p.data(), (int)pairs.size(), buf.data(), need, stats), 0), "jointCovariances");
         return split_blocks(buf, (int64_t)pairs.size(), 2 * d);
     }
+    // the 2D x 2D covariance [[Saa, Sab], [Sba, Sbb]] of each pair of distinct vertices, with or without a common edge
+    std::vector<MatrixXd> pairCovariances(const std::vector<std::pair<int, int>> &pairs, int fixed_id = -1, spg_cov_solve_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g);
+        std::vector<int32_t> p;
+        for (auto &q : pairs) { p.push_back(q.first); p.push_back(q.second); }
+        int64_t need = spg_graph_pair_covariances(_g, fixed_id, p.data(), (int)pairs.size(), nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(need, 0), "pairCovariances");
+        std::vector<double> buf((size_t)std::max<int64_t>(need, 1));
+        check((int)std::min<int64_t>(spg_graph_pair_covariances(_g, fixed_id, p.data(), (int)pairs.size(), buf.data(), need, stats), 0), "pairCovariances");
+        return split_blocks(buf, (int64_t)pairs.size(), 2 * d);
+    }
+    // GraphWrapperISAM::covariance (src/graph_wrapper_isam.cpp:259-262): the (nD) x (nD) joint covariance of the listed
+    // vertices in the order given, off-diagonal blocks mirrored exactly
+    MatrixXd jointMarginalCovariance(const std::vector<int> &ids, int fixed_id = -1, spg_cov_solve_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g);
+        std::vector<int32_t> w(ids.begin(), ids.end());
+        int64_t need = spg_graph_joint_marginal_covariance(_g, fixed_id, w.data(), (int)w.size(), nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(need, 0), "jointMarginalCovariance");
+        std::vector<double> buf((size_t)std::max<int64_t>(need, 1));
+        check((int)std::min<int64_t>(spg_graph_joint_marginal_covariance(_g, fixed_id, w.data(), (int)w.size(), buf.data(), need, stats), 0),
+              "jointMarginalCovariance");
+        return split_blocks(buf, 1, (int)w.size() * d)[0];
+    }
     // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
     // its marginal here, every vertex of `other` but the fixed one; ids ascending
     std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {

@@ -82,6 +82,17 @@ class CovStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CovSolveStats(C.Structure):
+    """spg_cov_solve_stats (include/spg.h)"""
+    _fields_ = [("cov", CovStats), ("columns", C.c_int32), ("rhs_batches", C.c_int32), ("solve_flops", C.c_double),
+                ("solve_seconds", C.c_double)]
+
+    def asdict(self):
+        d = self.cov.asdict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_[1:]})
+        return d
+
+
 class OptimizeStats(C.Structure):
     """spg_optimize_stats (include/spg.h)"""
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),

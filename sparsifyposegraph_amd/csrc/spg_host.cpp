@@ -32,6 +32,7 @@
 #endif
 #include <unistd.h>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 #include "../../include/spg.h"
 #include "spg_internal.h"
@@ -3652,6 +3653,101 @@ extern "C" int spg_graph_marginal_kld(spg_graph *base, spg_graph *other, int32_t
     std::copy(out_ids.begin(), out_ids.end(), ids);
     put_cov_stats(stats, secs, info);
     return nk;
+}
+
+// ================================================================================= covariance of arbitrary pairs / sets
+namespace {
+void put_cov_solve_stats(spg_cov_solve_stats *st, double secs, const double *info) {
+    if (!st) return;
+    put_cov_stats(&st->cov, secs, info);
+    st->columns = (int32_t)info[4]; st->rhs_batches = (int32_t)info[5];
+    st->solve_flops = info[6]; st->solve_seconds = info[7];
+}
+// D x D sub-blocks Sigma(va[i], vb[i]) (vertex indices) at out + dst[i], row stride ld
+int64_t cov_solve(spg_graph *g, int fixed, const std::vector<int32_t> &order, std::vector<int32_t> &va, std::vector<int32_t> &vb,
+                  const std::vector<int64_t> &dst, int32_t ld, int64_t need, double *out, spg_cov_solve_stats *stats, const char *what) {
+    spg_ctx *ctx = g->ctx;
+    if (!ctx->is_hip) {
+        snprintf(ctx->err, sizeof ctx->err, "%s needs the HIP backend", what);
+        return SPG_ESTATE;
+    }
+    for (int32_t &v : va) if (v == fixed) v = -1;
+    for (int32_t &v : vb) if (v == fixed) v = -1;
+    double secs = 0, info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (need == 0 || order.size() < 2) {   // nothing but the fixed vertex: every block is zero
+        std::fill(out, out + need, 0.0);
+        put_cov_solve_stats(stats, secs, info);
+        return need;
+    }
+    if (int rc = sync_device(g)) return rc;
+    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+    DenseStage st;
+    stage_free_vertices(g, order, fixed, st);
+    ctx->err[0] = 0;
+    int rc = spg::hip_sparse_cov_solve(spg::hip_backend_stream(&ctx->be), st.in, va.data(), vb.data(), dst.data(), ld, (int64_t)va.size(), need, out,
+                                       &secs, info, ctx->err, sizeof ctx->err);
+    if (rc) return rc;
+    put_cov_solve_stats(stats, secs, info);
+    return need;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_pair_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                              spg_cov_solve_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_pair_covariances: the fixed vertex is not in the graph");
+    const int D = g->d;
+    const int64_t W = 2 * D, need = (int64_t)n * W * W;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    for (int i = 0; i < n; i++) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        const int ia = live_index(g, a), ib = live_index(g, b);
+        const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_pair_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
+            return SPG_EINVAL;
+        }
+        if (!out || cap < need) continue;
+        const int32_t v[2] = {ia, ib};
+        for (int ka = 0; ka < 2; ka++)
+            for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(i * W * W + ka * D * W + kb * D); }
+    }
+    if (!out || cap < need) return need;
+    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_pair_covariances");
+}
+
+extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                                       spg_cov_solve_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !ids)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_marginal_covariance: the fixed vertex is not in the graph");
+    const int D = g->d;
+    const int64_t W = (int64_t)n * D, need = W * W;
+    if (W > 46000)
+        return set_err(g->ctx, SPG_ECAPACITY, "spg_graph_joint_marginal_covariance: limited to 46k variables, the bound of spg_graph_covariance");
+    std::vector<int32_t> idx((size_t)n);
+    {
+        std::unordered_set<int32_t> seen;
+        for (int i = 0; i < n; i++) {
+            idx[i] = live_index(g, ids[i]);
+            const char *why = idx[i] < 0 ? "is not in the graph" : !seen.insert(ids[i]).second ? "is listed twice" : nullptr;
+            if (why) {
+                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_marginal_covariance: vertex %d %s", (int)ids[i], why);
+                return SPG_EINVAL;
+            }
+        }
+    }
+    if (!out || cap < need) return need;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    va.reserve((size_t)n * n); vb.reserve((size_t)n * n); dst.reserve((size_t)n * n);
+    for (int a = 0; a < n; a++)
+        for (int b = 0; b < n; b++) { va.push_back(idx[a]); vb.push_back(idx[b]); dst.push_back((int64_t)a * D * W + (int64_t)b * D); }
+    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_joint_marginal_covariance");
 }
 
 // ================================================================================= optimize() (8f.1)

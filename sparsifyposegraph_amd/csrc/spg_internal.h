@@ -92,6 +92,13 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &o
 // info[4] += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops; *seconds += device time.
 int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, double *seconds, double *info,
                           char *err, size_t errlen);
+// Covariance sub-blocks of arbitrary vertex pairs (spg_sparse.inc): sub-block i = Sigma(va[i], vb[i]) (D x D; -1 = the
+// fixed vertex, zero) lands at out[dst[i]] with row stride ld (host, out_len doubles). Diagonal and in-pattern blocks
+// come from the selected inverse, the others from multi-RHS column solves through the fronts. info[8] += supernodes,
+// bytes of fronts and Z blocks, factorisation flops, selected-inverse flops, columns solved, RHS batches, solve flops,
+// solve seconds; *seconds += device time of everything.
+int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                         int64_t out_len, double *out, double *seconds, double *info, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -24,7 +24,10 @@
 // Per-pose covariances run the same recurrence over every supernode of the graph's own plan and read the requested
 // blocks out of the fronts (sp_sigma_blocks_kernel; per-vertex marginal KLD: sp_marginal_kld_kernel).
 #include <cstdlib>
+#include <cstring>
 #include <memory>
+#include <queue>
+#include <unordered_map>
 
 #include "spg_sparse_plan.hpp"
 
@@ -409,6 +412,76 @@ __global__ __launch_bounds__(64) void sp_sigma_blocks_kernel(FrontSink fs, const
         }
         o[e] = v;
     }
+}
+
+// ---- columns of Sigma by multi-right-hand-side solves through the fronts (spg_graph_pair_covariances and
+// spg_graph_joint_marginal_covariance). A batch solves R right-hand sides (D identity columns per column vertex) over
+// the union of the root paths it needs; every touched front s owns a row-major ld(s) x R panel in one workspace. The
+// tile products of the sweeps are items of sp_gemm_items_kernel; the kernels below move panel rows between fronts.
+struct PanelPair {       // child <-> parent panel rows: child boundary row t <-> parent row rel[t / D] + t % D
+    double *child;       // the child's panel at its first boundary row
+    double *parent;      // the parent's panel
+    const int32_t *rel;
+    int32_t nrows;       // child boundary rows in scalars
+    int32_t R;           // panel width
+};
+
+// GATHER = false: parent rows += child's update rows (forward; one launch per child rank, fixed order).
+// GATHER = true: child's boundary rows <- the parent's solved unknowns (backward). blockIdx = (pair, 64-column tile,
+// 64-row chunk), four wavefronts of 16 rows each; lane = column. Every destination element has one writer per launch.
+template <int D, bool GATHER>
+__global__ __launch_bounds__(256) void sp_panel_rows_kernel(const PanelPair *pairs) {
+    const PanelPair pr = pairs[blockIdx.x];
+    const int col = blockIdx.y * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
+    for (int k = 0; k < 16; k++) {
+        const int t = blockIdx.z * 64 + w * 16 + k;
+        if (t >= pr.nrows) return;
+        const int q = t / D;
+        double *c = pr.child + (long long)t * pr.R + col;
+        double *p = pr.parent + (long long)(pr.rel[q] + t - q * D) * pr.R + col;
+        if (GATHER) *c = *p;
+        else *p += *c;
+    }
+}
+
+// ws[at[i]] = 1: the identity columns of a batch's column vertices, in their fronts' pivot rows
+__global__ void sp_panel_seed_kernel(double *ws, const int64_t *at, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ws[at[i]] = 1.0;
+}
+
+// cross[dst[i] D^2 + r D + c] = ws[src[i] + r R + c]: the solved rows of request i (D x D, row-major)
+__global__ void sp_cross_rows_kernel(const double *ws, const int64_t *src, const int32_t *dst, int n, int D, int R, double *cross) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * D * D) return;
+    const int i = idx / (D * D), e = idx - i * D * D, r = e / D, c = e - r * D;
+    cross[(long long)dst[i] * D * D + e] = ws[src[i] + (long long)r * R + c];
+}
+
+// One D x D output sub-block of a pair / set covariance: out[dst + r ld + c]. cross >= 0: from the solved cross blocks
+// (transposed when the solved column was the other vertex); else pa, pb >= 0: from the selected inverse in the fronts,
+// read as sp_sigma_blocks_kernel reads it; else zero (the fixed vertex).
+struct CovBlk {
+    int64_t dst;
+    int32_t ld, pa, pb, cross, tr, pad_;
+};
+template <int D>
+__global__ __launch_bounds__(256) void sp_cov_assemble_kernel(FrontSink fs, const CovBlk *blks, int n, const double *cross, double *out) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= n || lane >= D * D) return;
+    const CovBlk b = blks[i];
+    const int r = lane / D, c = lane - r * D;
+    double v = 0.0;
+    if (b.cross >= 0) {
+        v = cross[(long long)b.cross * D * D + (b.tr ? c * D + r : r * D + c)];
+    } else if (b.pa >= 0 && b.pb >= 0) {
+        const bool lower = b.pa >= b.pb;
+        const int pv = lower ? b.pa : b.pb, pu = lower ? b.pb : b.pa, rr = lower ? r : c, cc = lower ? c : r;
+        int ld; bool tr;
+        const double *blk = fs.locate(pv, pu, ld, tr, true);
+        if (blk) v = tr ? blk[(long long)cc * ld + rr] : blk[(long long)rr * ld + cc];
+    }
+    out[b.dst + (long long)r * b.ld + c] = v;
 }
 
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
@@ -873,6 +946,343 @@ void plan_of(const spg::DenseGraphIn &in, const uint8_t *is_marg_vertex, spg::sp
     for (int v = 0; v < in.nv; v++) if (blk[v] >= 0) pos[v] = in.D * plan.iperm[blk[v]];
 }
 
+// ---- columns of Sigma through the fronts (host half of sp_panel_rows_kernel & co.)
+// Sigma[:, b] = L^-T L^-1 E_b. The forward sweep of E_b is non-zero only on the fronts of the path from b's supernode to
+// the root; the backward sweep restricted to the rows of a vertex a needs only the path from the root down to a's
+// supernode (boundary values are the ancestors' solved unknowns, gathered from the parent's panel). A batch of columns
+// therefore runs over the union of those paths only, level by level like the single-RHS solves, and must run on the
+// intact factor: before selected_inverse, which overwrites L_SS and L_BS (the diagonal-tile inverses survive).
+bool cov_force_solve() {
+    static const bool v = [] { const char *e = getenv("SPG_COV_FORCE_SOLVE"); return e && e[0] == '1'; }();
+    return v;
+}
+
+// block (qa, qb) of positions lies inside the fronts, where FrontSink::locate finds Sigma after the selected inverse
+bool in_fronts(const Plan &P, int qa, int qb) {
+    const int qu = std::min(qa, qb), qv = std::max(qa, qb), s = P.sn_of[qu];
+    if (qv < P.first[s + 1]) return true;
+    return std::binary_search(P.rows.begin() + P.rowptr[s], P.rows.begin() + P.rowptr[s + 1], qv);
+}
+
+// Greedy column cover: request i = block pair (x[i], y[i]) needs the column of x[i] or of y[i]; the block with the most
+// uncovered requests is solved first (ties: the earlier position), a diagonal request (x == y) needs its own column.
+void choose_columns(int nblocks, const std::vector<int32_t> &x, const std::vector<int32_t> &y, std::vector<int32_t> &col) {
+    const size_t m = x.size();
+    std::vector<int32_t> deg((size_t)nblocks, 0), ptr((size_t)nblocks + 1, 0), inc;
+    for (size_t i = 0; i < m; i++) { ptr[x[i] + 1]++; if (y[i] != x[i]) ptr[y[i] + 1]++; }
+    for (int v = 0; v < nblocks; v++) { deg[v] = ptr[v + 1]; ptr[v + 1] += ptr[v]; }
+    inc.resize((size_t)ptr[nblocks]);
+    {
+        std::vector<int32_t> f(ptr.begin(), ptr.end() - 1);
+        for (size_t i = 0; i < m; i++) { inc[f[x[i]]++] = (int32_t)i; if (y[i] != x[i]) inc[f[y[i]]++] = (int32_t)i; }
+    }
+    col.assign(m, -1);
+    auto take = [&](int v) {
+        for (int32_t k = ptr[v]; k < ptr[v + 1]; k++) {
+            const int32_t i = inc[k];
+            if (col[i] >= 0) continue;
+            col[i] = v;
+            const int o = x[i] == v ? y[i] : x[i];
+            if (o != v) deg[o]--;
+        }
+        deg[v] = 0;
+    };
+    for (size_t i = 0; i < m; i++) if (x[i] == y[i] && col[i] < 0) take(x[i]);
+    std::priority_queue<std::pair<int32_t, int32_t>> pq;
+    for (int v = 0; v < nblocks; v++) if (deg[v] > 0) pq.push({deg[v], -v});
+    while (!pq.empty()) {
+        const auto [d, nv] = pq.top();
+        pq.pop();
+        const int v = -nv;
+        if (deg[v] == 0) continue;
+        if (deg[v] != d) { pq.push({deg[v], -v}); continue; }
+        take(v);
+    }
+}
+
+struct ColumnSolves {
+    enum Kind { GEMM, EXTADD, GATHER, SEED, CROSS };
+    struct Step { Kind kind; int64_t begin; int32_t count, gy, gz; };
+    SparseSolver &sp;
+    const Plan &P;
+    int D;
+    // requests: Sigma[row block, column block] -> cross[i]
+    std::vector<int32_t> cols;                  // column blocks, ascending position
+    std::vector<int32_t> rq_ptr, rq_row, rq_idx;  // per column: its requests' row blocks and cross indices
+    int per_batch = 1, nbatch = 0;
+    double flops = 0, seconds = 0;
+    std::vector<int32_t> fw, bw, stamp_list;
+    int32_t stamp = 0;
+    std::vector<int64_t> off;
+    ColumnSolves(SparseSolver &s_, const std::vector<int32_t> &row, const std::vector<int32_t> &col) : sp(s_), P(s_.plan), D(s_.D) {
+        const size_t m = row.size();
+        std::vector<int32_t> order(m);
+        for (size_t i = 0; i < m; i++) order[i] = (int32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return col[a] < col[b]; });
+        rq_ptr.push_back(0);
+        for (size_t k = 0; k < m; k++) {
+            const int32_t i = order[k];
+            if (cols.empty() || cols.back() != col[i]) { if (!cols.empty()) rq_ptr.push_back((int32_t)rq_row.size()); cols.push_back(col[i]); }
+            rq_row.push_back(row[i]);
+            rq_idx.push_back(i);
+        }
+        if (!cols.empty()) rq_ptr.push_back((int32_t)rq_row.size());
+        fw.assign((size_t)P.nsn, 0);
+        bw.assign((size_t)P.nsn, 0);
+        off.assign((size_t)P.nsn, -1);
+    }
+    int width(int b) const {   // panel width of batch b: D columns per column vertex, padded to 64
+        const int nc = std::min<int>(per_batch, (int)cols.size() - b * per_batch);
+        return (D * nc + 63) / 64 * 64;
+    }
+    // marks fw / bw with the current stamp; returns the panel scalars of the batch
+    int64_t touch(int b) {
+        stamp++;
+        const int c0 = b * per_batch, c1 = std::min<int>(c0 + per_batch, (int)cols.size());
+        auto up = [&](std::vector<int32_t> &mk, int q) {
+            for (int s = P.sn_of[q]; s >= 0 && mk[s] != stamp; s = P.parent[s]) mk[s] = stamp;
+        };
+        for (int c = c0; c < c1; c++) {
+            up(fw, cols[c]);
+            for (int32_t k = rq_ptr[c]; k < rq_ptr[c + 1]; k++) up(bw, rq_row[k]);
+        }
+        const int R = width(b);
+        int64_t len = 0;
+        for (int s : P.level_sn)
+            if (fw[s] == stamp || bw[s] == stamp) { off[s] = len; len += (int64_t)P.ld(s) * R; }
+        return len;
+    }
+    // panel width R_max (a multiple of 64 up to 512) and the largest batch workspace that fits in free HBM
+    int plan_batches(int64_t &ws_len, char *err, size_t errlen) {
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        const double avail = (double)free_b - (double)(1ull << 30);
+        for (int Rm = 512; Rm >= 64; Rm /= 2) {
+            per_batch = std::max(1, Rm / D);
+            nbatch = ((int)cols.size() + per_batch - 1) / per_batch;
+            ws_len = 0;
+            for (int b = 0; b < nbatch; b++) ws_len = std::max(ws_len, touch(b));
+            if ((double)ws_len * 8 + 64.0 * 1e6 <= avail) return 0;
+        }
+        snprintf(err, errlen, "covariance column solves: the right-hand-side panels of one batch need %.2f GB, %.2f GB of HBM are free",
+                 ws_len * 8e-9, free_b * 1e-9);
+        return SPG_ECAPACITY;
+    }
+    // host item lists of batch b over the panel workspace ws
+    std::vector<GemmItem> gi;
+    std::vector<PanelPair> pp;
+    std::vector<int64_t> seeds, csrc;
+    std::vector<int32_t> cdst;
+    std::vector<Step> steps;
+    void build(int b, double *ws) {
+        gi.clear(); pp.clear(); seeds.clear(); csrc.clear(); cdst.clear(); steps.clear();
+        touch(b);
+        const int R = width(b), CT = R / 64, c0 = b * per_batch, c1 = std::min<int>(c0 + per_batch, (int)cols.size());
+        const double *linv = (const double *)sp.linv.p;
+        auto W = [&](int s) { return ws + off[s]; };
+        auto F = [&](int s) { return (const double *)sp.front(s); };
+        auto gemm = [&](size_t b0) { if (gi.size() > b0) steps.push_back({GEMM, (int64_t)b0, (int32_t)(gi.size() - b0), 0, 0}); };
+        auto rows_step = [&](Kind k, size_t b0, int maxrows) {
+            if (pp.size() > b0) steps.push_back({k, (int64_t)b0, (int32_t)(pp.size() - b0), CT, (maxrows + 63) / 64});
+        };
+        for (int c = c0; c < c1; c++) {
+            const int q = cols[c], s = P.sn_of[q], j = c - c0;
+            for (int d = 0; d < D; d++) seeds.push_back(off[s] + (int64_t)(D * (q - P.first[s]) + d) * R + D * j + d);
+        }
+        steps.push_back({SEED, 0, (int32_t)seeds.size(), 0, 0});
+        std::vector<int> lv;
+        // forward: L y = E over the columns' root paths
+        for (int l = 0; l < P.nlevels; l++) {
+            lv.clear();
+            for (int i = P.level_ptr[l]; i < P.level_ptr[l + 1]; i++) if (fw[P.level_sn[i]] == stamp) lv.push_back(P.level_sn[i]);
+            if (lv.empty()) continue;
+            for (int k = 0;; k++) {   // the children's update rows, child rank by child rank
+                const size_t b0 = pp.size();
+                int maxrows = 0;
+                bool more = false;
+                for (int s : lv) {
+                    int rank = 0;
+                    for (int ci = P.childptr[s]; ci < P.childptr[s + 1]; ci++) {
+                        const int ch = P.child[ci];
+                        if (fw[ch] != stamp) continue;
+                        if (rank++ != k) { if (rank > k + 1) { more = true; break; } continue; }
+                        pp.push_back({W(ch) + (int64_t)P.NP[ch] * R, W(s), sp.dev.rel + P.rowptr[ch], D * P.nrows(ch), R});
+                        maxrows = std::max(maxrows, D * P.nrows(ch));
+                    }
+                }
+                rows_step(EXTADD, b0, maxrows);
+                if (!more) break;
+            }
+            int maxtp = 0;
+            for (int s : lv) maxtp = std::max(maxtp, P.NP[s] / 64);
+            for (int p = 0; p < maxtp; p++) {
+                size_t b0 = gi.size();
+                if (p > 0)   // y_p -= sum_{q < p} L(p, q) y_q
+                    for (int s : lv) {
+                        if (P.NP[s] / 64 <= p) continue;
+                        const int ld = P.ld(s);
+                        for (int c = 0; c < CT; c++)
+                            gi.push_back({W(s) + (int64_t)p * 64 * R + 64 * c, F(s) + (int64_t)p * 64 * ld, W(s) + 64 * c, R, ld, R, 64, 64 * R, p, GI_ACC | GI_NEG, 0});
+                    }
+                gemm(b0);
+                b0 = gi.size();
+                for (int s : lv) {   // y_p = L_pp^-1 y_p (in place: one K tile, read before written)
+                    if (P.NP[s] / 64 <= p) continue;
+                    for (int c = 0; c < CT; c++) {
+                        double *t = W(s) + (int64_t)p * 64 * R + 64 * c;
+                        gi.push_back({t, linv + P.loff[s] + (int64_t)p * 4096, t, R, 64, R, 0, 0, 1, 0, 0});
+                    }
+                }
+                gemm(b0);
+            }
+            const size_t b0 = gi.size();
+            for (int s : lv) {   // update rows for the parent: u -= L_BS y_S
+                const int ld = P.ld(s), T = ld / 64, TP = P.NP[s] / 64;
+                for (int r = TP; r < T; r++)
+                    for (int c = 0; c < CT; c++)
+                        gi.push_back({W(s) + (int64_t)r * 64 * R + 64 * c, F(s) + (int64_t)r * 64 * ld, W(s) + 64 * c, R, ld, R, 64, 64 * R, TP, GI_ACC | GI_NEG, 0});
+            }
+            gemm(b0);
+        }
+        // backward: L^T x = y over the requested rows' root paths, top-down
+        for (int l = P.nlevels - 1; l >= 0; l--) {
+            lv.clear();
+            for (int i = P.level_ptr[l]; i < P.level_ptr[l + 1]; i++) if (bw[P.level_sn[i]] == stamp) lv.push_back(P.level_sn[i]);
+            if (lv.empty()) continue;
+            {
+                const size_t b0 = pp.size();
+                int maxrows = 0;
+                for (int s : lv) {
+                    if (P.parent[s] < 0 || P.nrows(s) == 0) continue;
+                    pp.push_back({W(s) + (int64_t)P.NP[s] * R, W(P.parent[s]), sp.dev.rel + P.rowptr[s], D * P.nrows(s), R});
+                    maxrows = std::max(maxrows, D * P.nrows(s));
+                }
+                rows_step(GATHER, b0, maxrows);
+            }
+            int maxtp = 0;
+            for (int s : lv) maxtp = std::max(maxtp, P.NP[s] / 64);
+            for (int st = 0; st < maxtp; st++) {
+                size_t b0 = gi.size();
+                for (int s : lv) {   // x_p = y_p - sum_{r > p} L(r, p)^T x_r
+                    const int ld = P.ld(s), T = ld / 64, TP = P.NP[s] / 64;
+                    if (TP <= st) continue;
+                    const int p = TP - 1 - st;
+                    if (T - p - 1 == 0) continue;
+                    for (int c = 0; c < CT; c++)
+                        gi.push_back({W(s) + (int64_t)p * 64 * R + 64 * c, F(s) + (int64_t)(p + 1) * 64 * ld + 64 * p, W(s) + (int64_t)(p + 1) * 64 * R + 64 * c,
+                                      R, ld, R, 64 * ld, 64 * R, T - p - 1, GI_TA | GI_ACC | GI_NEG, 0});
+                }
+                gemm(b0);
+                b0 = gi.size();
+                for (int s : lv) {   // x_p = L_pp^-T x_p
+                    const int TP = P.NP[s] / 64;
+                    if (TP <= st) continue;
+                    const int p = TP - 1 - st;
+                    for (int c = 0; c < CT; c++) {
+                        double *t = W(s) + (int64_t)p * 64 * R + 64 * c;
+                        gi.push_back({t, linv + P.loff[s] + (int64_t)p * 4096, t, R, 64, R, 0, 0, 1, GI_TA, 0});
+                    }
+                }
+                gemm(b0);
+            }
+        }
+        for (int c = c0; c < c1; c++)
+            for (int32_t k = rq_ptr[c]; k < rq_ptr[c + 1]; k++) {
+                const int q = rq_row[k], s = P.sn_of[q];
+                csrc.push_back(off[s] + (int64_t)D * (q - P.first[s]) * R + D * (c - c0));
+                cdst.push_back(rq_idx[k]);
+            }
+        steps.push_back({CROSS, 0, (int32_t)csrc.size(), 0, 0});
+        for (const GemmItem &it : gi) flops += 2.0 * 64 * 64 * 64 * it.nk;
+    }
+    // every batch: panels zeroed, seeded, forward, backward, requested rows -> cross (n requests x D^2)
+    int run(hipStream_t s, double *cross, char *err, size_t errlen) {
+        int rc = 0;
+        int64_t ws_len = 0;
+        if (cols.empty()) return 0;
+        if ((rc = plan_batches(ws_len, err, errlen))) return rc;
+        DevBuf ws, blob;
+        size_t blob_cap = 0;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        std::vector<char> hb;
+        auto fail = [&](const char *what, hipError_t e) {
+            snprintf(err, errlen, "covariance column solves: %s failed: %s", what, hipGetErrorString(e));
+            return SPG_EHIP;
+        };
+        hipError_t e;
+        if ((e = hipMalloc(&ws.p, (size_t)std::max<int64_t>(ws_len, 1) * 8)) != hipSuccess) {
+            snprintf(err, errlen, "covariance column solves: hipMalloc of %.2f GB of panels failed", ws_len * 8e-9);
+            return SPG_ECAPACITY;
+        }
+        if ((e = hipEventCreate(&e0)) != hipSuccess || (e = hipEventCreate(&e1)) != hipSuccess) { rc = fail("hipEventCreate", e); goto out; }
+        for (int b = 0; b < nbatch; b++) {
+            build(b, (double *)ws.p);
+            // one upload per batch: gemm items | panel pairs | seeds | cross sources | cross destinations
+            const size_t o_pp = gi.size() * sizeof(GemmItem), o_sd = o_pp + pp.size() * sizeof(PanelPair), o_cs = o_sd + seeds.size() * 8,
+                         o_cd = o_cs + csrc.size() * 8, nbytes = o_cd + cdst.size() * 4;
+            hb.resize(nbytes);
+            memcpy(hb.data(), gi.data(), o_pp);
+            memcpy(hb.data() + o_pp, pp.data(), o_sd - o_pp);
+            memcpy(hb.data() + o_sd, seeds.data(), o_cs - o_sd);
+            memcpy(hb.data() + o_cs, csrc.data(), o_cd - o_cs);
+            memcpy(hb.data() + o_cd, cdst.data(), nbytes - o_cd);
+            if (b > 0) {   // the previous batch still reads the blob and the panels
+                float ms = 0;
+                if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = fail("a batch", e); goto out; }
+                if ((e = hipEventElapsedTime(&ms, e0, e1)) != hipSuccess) { rc = fail("hipEventElapsedTime", e); goto out; }
+                seconds += 1e-3 * ms;
+            }
+            if (nbytes > blob_cap) {
+                if (blob.p) { (void)hipFree(blob.p); blob.p = nullptr; }
+                blob_cap = nbytes + nbytes / 4;
+                if ((e = hipMalloc(&blob.p, blob_cap)) != hipSuccess) { rc = fail("hipMalloc of the item lists", e); goto out; }
+            }
+            if ((e = hipMemcpy(blob.p, hb.data(), nbytes, hipMemcpyHostToDevice)) != hipSuccess) { rc = fail("uploading the item lists", e); goto out; }
+            const char *B = (const char *)blob.p;
+            const int R = width(b);
+            int64_t len = 0;
+            for (int sn : P.level_sn) if (fw[sn] == stamp || bw[sn] == stamp) len += (int64_t)P.ld(sn) * R;
+            if ((e = hipEventRecord(e0, s)) != hipSuccess) { rc = fail("hipEventRecord", e); goto out; }
+            if ((e = hipMemsetAsync(ws.p, 0, (size_t)std::max<int64_t>(len, 1) * 8, s)) != hipSuccess) { rc = fail("hipMemsetAsync", e); goto out; }
+            for (const Step &st : steps) {
+                switch (st.kind) {
+                case GEMM:
+                    hipLaunchKernelGGL(sp_gemm_items_kernel, dim3(st.count), dim3(256), 0, s, (const GemmItem *)B + st.begin);
+                    break;
+                case EXTADD:
+                    if (D == 6) hipLaunchKernelGGL((sp_panel_rows_kernel<6, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    else hipLaunchKernelGGL((sp_panel_rows_kernel<3, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    break;
+                case GATHER:
+                    if (D == 6) hipLaunchKernelGGL((sp_panel_rows_kernel<6, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    else hipLaunchKernelGGL((sp_panel_rows_kernel<3, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    break;
+                case SEED:
+                    hipLaunchKernelGGL(sp_panel_seed_kernel, dim3((st.count + 255) / 256), dim3(256), 0, s, (double *)ws.p, (const int64_t *)(B + o_sd), st.count);
+                    break;
+                case CROSS:
+                    if (st.count > 0)
+                        hipLaunchKernelGGL(sp_cross_rows_kernel, dim3((st.count * D * D + 255) / 256), dim3(256), 0, s, (const double *)ws.p, (const int64_t *)(B + o_cs),
+                                           (const int32_t *)(B + o_cd), st.count, D, R, cross);
+                    break;
+                }
+            }
+            if ((e = hipGetLastError()) != hipSuccess) { rc = fail("a launch", e); goto out; }
+            if ((e = hipEventRecord(e1, s)) != hipSuccess) { rc = fail("hipEventRecord", e); goto out; }
+        }
+        {
+            float ms = 0;
+            if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = fail("a batch", e); goto out; }
+            if ((e = hipEventElapsedTime(&ms, e0, e1)) != hipSuccess) { rc = fail("hipEventElapsedTime", e); goto out; }
+            seconds += 1e-3 * ms;
+        }
+    out:
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return rc;
+    }
+};
+
 // Sparse linear algebra for LM: the fronts are re-assembled for every trial (the estimates of a trial are those
 // of its iteration), shifted by lambda, factorised, and the right-hand side is solved in place.
 struct SparseLM : LMLinear {
@@ -1112,6 +1522,109 @@ int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int
     if ((rc = sigma_blocks(s, in, K, req, n, (double *)dout.p, seconds, info, err, errlen))) goto done;
     if (n > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)n * W * W * 8, hipMemcpyDeviceToHost));
 done:
+    return rc;
+}
+
+// Covariance sub-blocks of arbitrary vertex pairs (spg_graph_pair_covariances / _joint_marginal_covariance). Sub-block i
+// is Sigma(va[i], vb[i]) (D x D, -1 = the fixed vertex: zero) at out + dst[i], row stride ld. Diagonal and in-pattern
+// sub-blocks are read from the selected inverse (bit for bit what sigma_blocks reads; SPG_COV_FORCE_SOLVE=1 sends them
+// through the solves as well); the others take one column solve per pair of vertices, shared by (a, b) and (b, a).
+// Order on the device: factorisation, column solves on the intact factor, selected inverse, one assembly launch.
+int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                         int64_t out_len, double *out, double *seconds, double *info, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int D = in_.D;
+    const bool force = cov_force_solve();
+    int rc = 0;
+    sparse::Plan plan;
+    std::vector<int32_t> pos;
+    plan_of(in_, nullptr, plan, pos);
+    for (int64_t i = 0; i < nblk; i++)
+        if ((va[i] >= 0 && pos[va[i]] < 0) || (vb[i] >= 0 && pos[vb[i]] < 0)) {
+            snprintf(err, errlen, "covariance blocks: a requested vertex is not a variable");
+            return SPG_ESTATE;
+        }
+    auto sp = std::make_unique<SparseSolver>();
+    const int nsn = plan.nsn, nblocks = plan.n;
+    const double fflops = plan.flops;
+    if ((rc = sp->init(std::move(plan), true, err, errlen))) return rc;
+    const Plan &P = sp->plan;
+    // sub-blocks -> selected inverse or a cross block; one cross block per unordered pair of positions
+    std::vector<CovBlk> blks((size_t)nblk);
+    std::vector<int32_t> cx, cy;    // cross requests: block positions x <= y
+    {
+        std::unordered_map<uint64_t, int32_t> key;
+        for (int64_t i = 0; i < nblk; i++) {
+            CovBlk &b = blks[i];
+            b = CovBlk{dst[i], ld, va[i] < 0 ? -1 : pos[va[i]], vb[i] < 0 ? -1 : pos[vb[i]], -1, 0, 0};
+            if (b.pa < 0 || b.pb < 0) { b.pa = b.pb = -1; continue; }
+            const int qa = b.pa / D, qb = b.pb / D;
+            if (!force && (qa == qb || in_fronts(P, qa, qb))) continue;
+            const int x = std::min(qa, qb), y = std::max(qa, qb);
+            auto it = key.emplace(((uint64_t)x << 32) | (uint32_t)y, (int32_t)cx.size());
+            if (it.second) { cx.push_back(x); cy.push_back(y); }
+            b.cross = it.first->second;
+        }
+    }
+    std::vector<int32_t> ccol, crow(cx.size());
+    choose_columns(nblocks, cx, cy, ccol);
+    for (size_t i = 0; i < cx.size(); i++) crow[i] = ccol[i] == cx[i] ? cy[i] : cx[i];
+    for (CovBlk &b : blks)   // the cross block holds Sigma(row, column): transposed when a is the solved column
+        if (b.cross >= 0) b.tr = (b.pa / D == ccol[b.cross] && b.pa != b.pb) ? 1 : 0;
+    ColumnSolves cs(*sp, crow, ccol);
+    DenseGraphIn in = in_;
+    in.pos = pos.data();
+    GraphBufs gb;
+    DevBuf bad, dout, dcross, dblk;
+    int h_bad[2] = {0, 0};
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+    float ms0 = 0, ms1 = 0;
+    HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
+    HIPCHK(hipMalloc(&dout.p, (size_t)std::max<int64_t>(out_len, 1) * 8));
+    HIPCHK(hipMalloc(&dcross.p, std::max<size_t>(cx.size(), 1) * D * D * 8));
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventCreate(&e2));
+    HIPCHK(hipEventCreate(&e3));
+    if ((rc = upload(dblk, blks.data(), blks.size(), s)) || (rc = stage_graph(in, gb, s))) {
+        snprintf(err, errlen, "staging the graph for the covariance blocks failed (%d)", rc);
+        goto done;
+    }
+    HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
+    HIPCHK(hipEventRecord(e0, s));
+    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); goto done; }
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
+    HIPCHK(hipEventElapsedTime(&ms0, e0, e1));
+    if ((rc = cs.run(s, (double *)dcross.p, err, errlen))) goto done;
+    HIPCHK(hipEventRecord(e2, s));
+    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); goto done; }
+    if (nblk > 0) {
+        const FrontSink fs{sp->dev, (int *)bad.p + 1};
+        const dim3 g((unsigned)((nblk + 3) / 4)), b(256);
+        if (D == 6) hipLaunchKernelGGL((sp_cov_assemble_kernel<6>), g, b, 0, s, fs, (const CovBlk *)dblk.p, (int)nblk, (const double *)dcross.p, (double *)dout.p);
+        else hipLaunchKernelGGL((sp_cov_assemble_kernel<3>), g, b, 0, s, fs, (const CovBlk *)dblk.p, (int)nblk, (const double *)dcross.p, (double *)dout.p);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e3, s));
+    HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipEventElapsedTime(&ms1, e2, e3));
+    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
+    if (h_bad[1]) { snprintf(err, errlen, "covariance blocks: a requested pair lies outside the fronts of the factorisation"); rc = SPG_ESTATE; goto done; }
+    if (out_len > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)out_len * 8, hipMemcpyDeviceToHost));
+    if (seconds) *seconds += 1e-3 * (ms0 + ms1) + cs.seconds;
+    if (info) {
+        info[0] += nsn; info[1] += (double)(P.pool + sp->zpool_len) * 8; info[2] += fflops; info[3] += sp->selinv_flops;
+        info[4] += (double)cs.cols.size(); info[5] += cs.nbatch; info[6] += cs.flops; info[7] += cs.seconds;
+    }
+done:
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e2) (void)hipEventDestroy(e2);
+    if (e3) (void)hipEventDestroy(e3);
     return rc;
 }
 

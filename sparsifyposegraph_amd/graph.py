@@ -290,6 +290,35 @@ class GraphWrapperHIP:
         self.last_covariance_stats = st.asdict()
         return out
 
+    def pairCovariances(self, pairs, fixed_id=-1):
+        """The 2D x 2D covariance [[Saa, Sab], [Sba, Sbb]] of each pair (a, b) of distinct vertices, with or without a
+        common edge: in-pattern blocks from the selected inverse, the others from column solves through the sparse
+        factor. Returns float64[n, 2D, 2D]. Stats (abi.CovSolveStats) in `last_covariance_stats`."""
+        d, st = self.d, abi.CovSolveStats()
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = self.L.spg_graph_pair_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), None, 0, None)
+        check(min(int(n), 0), self.ctx.h, "pairCovariances")
+        out = np.zeros((len(pr), 2 * d, 2 * d))
+        rc = self.L.spg_graph_pair_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), _p(out, C.c_double), out.size, C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "pairCovariances")
+        self.last_covariance_stats = st.asdict()
+        return out
+
+    def jointMarginalCovariance(self, ids, fixed_id=-1):
+        """GraphWrapperISAM::covariance (src/graph_wrapper_isam.cpp:259-262), covariances().marginal(ids): the (nD) x (nD)
+        joint covariance of n distinct vertices in the order given; off-diagonal blocks mirrored exactly. Returns float64[nD, nD]. Stats
+        (abi.CovSolveStats) in `last_covariance_stats`."""
+        d, st = self.d, abi.CovSolveStats()
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        n = self.L.spg_graph_joint_marginal_covariance(self.h, int(fixed_id), _p(ids, C.c_int32), len(ids), None, 0, None)
+        check(min(int(n), 0), self.ctx.h, "jointMarginalCovariance")
+        out = np.zeros((len(ids) * d, len(ids) * d))
+        rc = self.L.spg_graph_joint_marginal_covariance(self.h, int(fixed_id), _p(ids, C.c_int32), len(ids), _p(out, C.c_double), out.size,
+                                                        C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "jointMarginalCovariance")
+        self.last_covariance_stats = st.asdict()
+        return out
+
     def marginalKullbackLeibler(self, other, fixed_id=-1):
         """Called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other`
         against its marginal here, for every vertex of `other` but the fixed one. Returns (ids, kld), ascending ids.

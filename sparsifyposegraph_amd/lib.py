@@ -69,6 +69,8 @@ SYMBOLS = {
     "spg_graph_marginal_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovStats)]),
     "spg_graph_joint_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovStats)]),
     "spg_graph_marginal_kld": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int, C.POINTER(abi.CovStats)]),
+    "spg_graph_pair_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
+    "spg_graph_joint_marginal_covariance": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_sparse_plan": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.POINTER(abi.SparsePlanInfo),
                                   _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int64]),
