@@ -23,6 +23,7 @@
 #include <cmath>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "spg_dev_geom.hpp"
@@ -44,13 +45,13 @@ __device__ __forceinline__ double readlane64(double v, int lane) {
     return r.d;
 }
 
+// needs `char *err, size_t errlen` in scope; everything a driver holds is RAII (DevBuf, EventTimer), so it just returns
 #define HIPCHK(x)                                                                                              \
     do {                                                                                                       \
         hipError_t e_ = (x);                                                                                   \
         if (e_ != hipSuccess) {                                                                                \
             snprintf(err, errlen, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);     \
-            rc = SPG_EHIP;                                                                                     \
-            goto done;                                                                                         \
+            return SPG_EHIP;                                                                                   \
         }                                                                                                      \
     } while (0)
 
@@ -1144,6 +1145,30 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// A span of stream work timed by a pair of HIP events: start(s) ... stop(s), and ms() once the stream is synchronised.
+struct EventTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t made;
+    EventTimer() { made = hipEventCreate(&e0); if (made == hipSuccess) made = hipEventCreate(&e1); }
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    hipError_t start(hipStream_t s) { return made != hipSuccess ? made : hipEventRecord(e0, s); }
+    hipError_t stop(hipStream_t s) { return hipEventRecord(e1, s); }
+    hipError_t ms(float &out) { return hipEventElapsedTime(&out, e0, e1); }
+};
+
+// The pose dimension as a compile-time constant: f(std::integral_constant<int, 6>) or <3>, e.g.
+// by_dim(D, [&](auto d) { hipLaunchKernelGGL((kernel<decltype(d)::value>), ...); })
+template <class F>
+auto by_dim(int D, F &&f) {
+    if (D == 6) return f(std::integral_constant<int, 6>{});
+    return f(std::integral_constant<int, 3>{});
+}
+
 template <class T>
 int upload(DevBuf &b, const T *src, size_t n, hipStream_t s) {
     size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
@@ -1226,6 +1251,17 @@ void launch_assemble_into(const GraphBufs &gb, Sink sink, hipStream_t s, double 
 template <int D>
 void launch_assemble(const GraphBufs &gb, double *M, int ld, hipStream_t s, double *bvec = nullptr) {
     launch_assemble_into<D>(gb, DenseSink{M, ld}, s, bvec);
+}
+
+void launch_assemble(int D, const GraphBufs &gb, double *M, int ld, hipStream_t s, double *bvec = nullptr) {
+    by_dim(D, [&](auto d) { launch_assemble<decltype(d)::value>(gb, M, ld, s, bvec); });
+}
+
+// diff[i] = estimate difference of kept vertex i between the two arenas (pose_diff_kernel)
+void launch_pose_diff(int D, hipStream_t s, const void *arena_b, const int64_t *vpo_b, const void *arena_o, const int64_t *vpo_o, int nk, double *diff) {
+    by_dim(D, [&](auto d) {
+        hipLaunchKernelGGL((pose_diff_kernel<decltype(d)::value>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)arena_b, vpo_b, (const double *)arena_o, vpo_o, nk, diff);
+    });
 }
 
 constexpr int kSmallTileSteps = 128;   // steps of at most this many 128-tiles take tile_abt_small_kernel
@@ -1361,19 +1397,17 @@ struct Carver {      // offsets into a block, 256-byte aligned
 template <int D>
 static int big_glc_dense_impl(hipStream_t s, const spg::DenseGraphIn &in, int m, int k, int Nm, int64_t new_off, double *orec, int n_new_max, int tag,
                               double *seconds, char *err, size_t errlen) {
-    int rc = 0;
     constexpr int DD = D * D;
     const int n = D * k, nm = D * m, Ng = round_up(std::max(n, 1)), N = Nm + Ng, Nr = round_up(std::max(n - D, 1)), ntr = Nr / TB;
     double *arena = (double *)const_cast<void *>(in.dev_arena);
     const int np = 256;
-    float ms = 0;
     BigPool &P = big_pool();
     std::lock_guard<std::mutex> lock(P.mu);
     int dev_now = 0;
     GraphBufs gb;                      // (its DevBufs stay empty: everything lives in the pool)
     std::vector<int64_t> awoff;
     int64_t aw_total = 0;
-    if ((rc = plan_graph(in, gb, awoff, aw_total))) { snprintf(err, errlen, "staging a large blanket failed (%d)", rc); return rc; }
+    if (int rc = plan_graph(in, gb, awoff, aw_total)) { snprintf(err, errlen, "staging a large blanket failed (%d)", rc); return rc; }
     // ---- layout: matrices, small state, then the staged block (the graph arrays), mirrored in pinned memory
     Carver dc, pc;
     const size_t oH = dc.take((size_t)N * N * 8), oY = dc.take((size_t)Ng * Ng * 8), oMt = dc.take((size_t)Ng * Ng * 8);
@@ -1408,71 +1442,69 @@ static int big_glc_dense_impl(hipStream_t s, const spg::DenseGraphIn &in, int m,
         if (!P.e0) { HIPCHK(hipEventCreate(&P.e0)); HIPCHK(hipEventCreate(&P.e1)); }
         P.device = dev_now;
     }
+    double *H = (double *)(P.dev + oH), *Y = (double *)(P.dev + oY), *Mt = (double *)(P.dev + oMt), *Mrel = (double *)(P.dev + oMrel), *Yi = (double *)(P.dev + oYi);
+    double *linv = (double *)(P.dev + oLinv), *linv_all = (double *)(P.dev + oLinvAll), *partial = (double *)(P.dev + oPartial);
+    double *jinv = (double *)(P.dev + oJinv), *meas = (double *)(P.dev + oMeas);
+    int *flags = (int *)(P.dev + oState);
+    double *stats = (double *)(P.dev + oState + 64);
+    char *staged = P.dev + oStaged;
+    // ---- the staged block
+    memcpy(P.pin + sPos, in.pos, (size_t)in.nv * 4);
+    memcpy(P.pin + sVpo, in.vpo, (size_t)in.nv * 8);
+    memcpy(P.pin + sRow, in.rowptr, ((size_t)in.nv + 1) * 4);
+    if (n_inc) memcpy(P.pin + sInc, in.inc, n_inc * 4);
+    if (in.ne) memcpy(P.pin + sEr, in.er, (size_t)in.ne * sizeof(spg_edge_ref));
+    if (in.n_ev) memcpy(P.pin + sEv, in.ev, (size_t)in.n_ev * 4);
+    if (in.ne) memcpy(P.pin + sAwoff, awoff.data(), (size_t)in.ne * 8);
+    HIPCHK(hipMemcpyAsync(staged, P.pin, pc.used, hipMemcpyHostToDevice, s));
+    gb.dev = GraphDev{(const double *)in.dev_arena, (const int32_t *)(staged + sPos), (const int64_t *)(staged + sVpo),
+                      (const int32_t *)(staged + sRow), (const int32_t *)(staged + sInc), (const spg_edge_ref *)(staged + sEr),
+                      (const int32_t *)(staged + sEv), (const int64_t *)(staged + sAwoff), (double *)(P.dev + oAw), in.nv, in.ne};
+    HIPCHK(hipEventRecord(P.e0, s));
+    HIPCHK(hipMemsetAsync(H, 0, (size_t)N * N * 8, s));
+    HIPCHK(hipMemsetAsync(Mrel, 0, (oYi - oMrel) + (size_t)Nr * Nr * 8, s));      // M_rel and Yi
+    HIPCHK(hipMemsetAsync(flags, 0, 256, s));
+    launch_assemble<D>(gb, H, N, s);
+    if (Nm > nm) hipLaunchKernelGGL(pad_identity_kernel, dim3((Nm - nm + 255) / 256), dim3(256), 0, s, H, N, nm, Nm);
+    if (Ng > n) hipLaunchKernelGGL(pad_identity_kernel, dim3((Ng - n + 255) / 256), dim3(256), 0, s, H, N, Nm + n, N);
+    // Schur complement onto the kept block: the factorisation stops where that block begins
+    potrf_lower(H, N, linv, flags, s, Nm / TB);
+    const double *Lam = H + ((long long)Nm * N + Nm);
+    BigArrow ar{jinv, meas};
+    hipLaunchKernelGGL((big_reparam_kernel<D>), dim3((k + 63) / 64), dim3(64), 0, s, (const double *)arena, gb.dev.vpo, m, k, ar, flags + 1);
+    if (k > 1) hipLaunchKernelGGL((big_arrow_finish_kernel<D>), dim3((k + 62) / 64), dim3(64), 0, s, k, ar);
+    hipLaunchKernelGGL((big_right_mul_kernel<D>), dim3(n), dim3(64), 0, s, Lam, N, k, (const double *)jinv, Y, Ng);
+    hipLaunchKernelGGL((big_left_mul_kernel<D>), dim3(n - D + (n + 63) / 64), dim3(256), 0, s, (const double *)Y, Ng, k, (const double *)jinv, Mt, Ng);
+    hipLaunchKernelGGL((big_extract_kernel<D>), dim3(256), dim3(256), 0, s, (const double *)Mt, Ng, n, Mrel, Nr, stats);
+    if (Nr > n - D) hipLaunchKernelGGL(pad_identity_kernel, dim3((Nr - (n - D) + 255) / 256), dim3(256), 0, s, Mrel, Nr, n - D, Nr);
+    hipLaunchKernelGGL(pad_identity_kernel, dim3((Nr + 255) / 256), dim3(256), 0, s, Yi, Nr, 0, Nr);
+    // lambda_min(M_rel) > 1e-8 is proven by trace(M_rel^-1) = ||L^-T||_F^2 < 1e8
+    potrf_lower(Mrel, Nr, linv, flags + 2, s, -1, linv_all);
+    rsolve_lower_transposed(Yi, Nr, Mrel, Nr, Nr, linv_all, flags + 3, s, true);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(np), dim3(256), 0, s, (const double *)Yi, Nr, n - D, partial);
+    const long long rec_len = (long long)n + (long long)(n - D) * n;
+    hipLaunchKernelGGL((big_write_record_kernel<D>), dim3(512), dim3(256), 0, s, (const double *)Mrel, Nr, n, (const double *)meas, arena + new_off);
     {
-        double *H = (double *)(P.dev + oH), *Y = (double *)(P.dev + oY), *Mt = (double *)(P.dev + oMt), *Mrel = (double *)(P.dev + oMrel), *Yi = (double *)(P.dev + oYi);
-        double *linv = (double *)(P.dev + oLinv), *linv_all = (double *)(P.dev + oLinvAll), *partial = (double *)(P.dev + oPartial);
-        double *jinv = (double *)(P.dev + oJinv), *meas = (double *)(P.dev + oMeas);
-        int *flags = (int *)(P.dev + oState);
-        double *stats = (double *)(P.dev + oState + 64);
-        char *staged = P.dev + oStaged;
-        // ---- the staged block
-        memcpy(P.pin + sPos, in.pos, (size_t)in.nv * 4);
-        memcpy(P.pin + sVpo, in.vpo, (size_t)in.nv * 8);
-        memcpy(P.pin + sRow, in.rowptr, ((size_t)in.nv + 1) * 4);
-        if (n_inc) memcpy(P.pin + sInc, in.inc, n_inc * 4);
-        if (in.ne) memcpy(P.pin + sEr, in.er, (size_t)in.ne * sizeof(spg_edge_ref));
-        if (in.n_ev) memcpy(P.pin + sEv, in.ev, (size_t)in.n_ev * 4);
-        if (in.ne) memcpy(P.pin + sAwoff, awoff.data(), (size_t)in.ne * 8);
-        HIPCHK(hipMemcpyAsync(staged, P.pin, pc.used, hipMemcpyHostToDevice, s));
-        gb.dev = GraphDev{(const double *)in.dev_arena, (const int32_t *)(staged + sPos), (const int64_t *)(staged + sVpo),
-                          (const int32_t *)(staged + sRow), (const int32_t *)(staged + sInc), (const spg_edge_ref *)(staged + sEr),
-                          (const int32_t *)(staged + sEv), (const int64_t *)(staged + sAwoff), (double *)(P.dev + oAw), in.nv, in.ne};
-        HIPCHK(hipEventRecord(P.e0, s));
-        HIPCHK(hipMemsetAsync(H, 0, (size_t)N * N * 8, s));
-        HIPCHK(hipMemsetAsync(Mrel, 0, (oYi - oMrel) + (size_t)Nr * Nr * 8, s));      // M_rel and Yi
-        HIPCHK(hipMemsetAsync(flags, 0, 256, s));
-        launch_assemble<D>(gb, H, N, s);
-        if (Nm > nm) hipLaunchKernelGGL(pad_identity_kernel, dim3((Nm - nm + 255) / 256), dim3(256), 0, s, H, N, nm, Nm);
-        if (Ng > n) hipLaunchKernelGGL(pad_identity_kernel, dim3((Ng - n + 255) / 256), dim3(256), 0, s, H, N, Nm + n, N);
-        // Schur complement onto the kept block: the factorisation stops where that block begins
-        potrf_lower(H, N, linv, flags, s, Nm / TB);
-        const double *Lam = H + ((long long)Nm * N + Nm);
-        BigArrow ar{jinv, meas};
-        hipLaunchKernelGGL((big_reparam_kernel<D>), dim3((k + 63) / 64), dim3(64), 0, s, (const double *)arena, gb.dev.vpo, m, k, ar, flags + 1);
-        if (k > 1) hipLaunchKernelGGL((big_arrow_finish_kernel<D>), dim3((k + 62) / 64), dim3(64), 0, s, k, ar);
-        hipLaunchKernelGGL((big_right_mul_kernel<D>), dim3(n), dim3(64), 0, s, Lam, N, k, (const double *)jinv, Y, Ng);
-        hipLaunchKernelGGL((big_left_mul_kernel<D>), dim3(n - D + (n + 63) / 64), dim3(256), 0, s, (const double *)Y, Ng, k, (const double *)jinv, Mt, Ng);
-        hipLaunchKernelGGL((big_extract_kernel<D>), dim3(256), dim3(256), 0, s, (const double *)Mt, Ng, n, Mrel, Nr, stats);
-        if (Nr > n - D) hipLaunchKernelGGL(pad_identity_kernel, dim3((Nr - (n - D) + 255) / 256), dim3(256), 0, s, Mrel, Nr, n - D, Nr);
-        hipLaunchKernelGGL(pad_identity_kernel, dim3((Nr + 255) / 256), dim3(256), 0, s, Yi, Nr, 0, Nr);
-        // lambda_min(M_rel) > 1e-8 is proven by trace(M_rel^-1) = ||L^-T||_F^2 < 1e8
-        potrf_lower(Mrel, Nr, linv, flags + 2, s, -1, linv_all);
-        rsolve_lower_transposed(Yi, Nr, Mrel, Nr, Nr, linv_all, flags + 3, s, true);
-        hipLaunchKernelGGL(sumsq_kernel, dim3(np), dim3(256), 0, s, (const double *)Yi, Nr, n - D, partial);
-        const long long rec_len = (long long)n + (long long)(n - D) * n;
-        hipLaunchKernelGGL((big_write_record_kernel<D>), dim3(512), dim3(256), 0, s, (const double *)Mrel, Nr, n, (const double *)meas, arena + new_off);
-        {
-            // the eigen route, taken inside the kernel only when the shortcut's guard failed: A in Y (free since the left
-            // multiplication), V and the small scratch in H (free since the Schur complement was read)
-            double *Vs = H, *cs = Vs + (size_t)Ng * Ng;
-            int *perm = reinterpret_cast<int *>(cs + 3 * n + 2);
-            static_assert(TB >= 16, "the scratch behind V assumes N^2 - Ng^2 >= 4 n + 2");
-            size_t eig_lds = n >= 128 ? ((size_t)6 * n + 8) * 8 : 0;
-            if (eig_lds > 140 * 1024) eig_lds = 0;      // (beyond 2 986 variables: the Jacobi sweeps, which need no LDS)
-            if (eig_lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(big_glc_eig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)eig_lds));
-            hipLaunchKernelGGL(big_glc_eig_kernel, dim3(1), dim3(256), eig_lds, s, flags, (const double *)stats, (const double *)partial, np,
-                               (const double *)Mt, Ng, n, n - D, Y, Vs, Ng, cs, perm, (const double *)meas, arena + new_off);
-        }
-        hipLaunchKernelGGL(big_out_record_kernel, dim3(1), dim3(256), 0, s, orec, (const int *)flags, (const double *)stats, (const double *)partial, np,
-                           n, D, m, k, n_new_max, tag, rec_len);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(P.e1, s));
-        HIPCHK(hipStreamSynchronize(s));   // the pool is laid out anew by the next call
-        HIPCHK(hipEventElapsedTime(&ms, P.e0, P.e1));
-        if (seconds) *seconds = 1e-3 * ms;
+        // the eigen route, taken inside the kernel only when the shortcut's guard failed: A in Y (free since the left
+        // multiplication), V and the small scratch in H (free since the Schur complement was read)
+        double *Vs = H, *cs = Vs + (size_t)Ng * Ng;
+        int *perm = reinterpret_cast<int *>(cs + 3 * n + 2);
+        static_assert(TB >= 16, "the scratch behind V assumes N^2 - Ng^2 >= 4 n + 2");
+        size_t eig_lds = n >= 128 ? ((size_t)6 * n + 8) * 8 : 0;
+        if (eig_lds > 140 * 1024) eig_lds = 0;      // (beyond 2 986 variables: the Jacobi sweeps, which need no LDS)
+        if (eig_lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(big_glc_eig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)eig_lds));
+        hipLaunchKernelGGL(big_glc_eig_kernel, dim3(1), dim3(256), eig_lds, s, flags, (const double *)stats, (const double *)partial, np,
+                           (const double *)Mt, Ng, n, n - D, Y, Vs, Ng, cs, perm, (const double *)meas, arena + new_off);
     }
-done:
-    return rc;
+    hipLaunchKernelGGL(big_out_record_kernel, dim3(1), dim3(256), 0, s, orec, (const int *)flags, (const double *)stats, (const double *)partial, np,
+                       n, D, m, k, n_new_max, tag, rec_len);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(P.e1, s));
+    HIPCHK(hipStreamSynchronize(s));   // the pool is laid out anew by the next call
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, P.e0, P.e1));
+    if (seconds) *seconds = 1e-3 * ms;
+    return 0;
 }
 
 }  // namespace
@@ -1483,24 +1515,20 @@ namespace spg {
 // output n x n row-major, full symmetric.
 int hip_dense_information(void *stream, const DenseGraphIn &in, int n, double *out, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
-    int rc = 0;
     const int N = round_up(std::max(n, 1));
     GraphBufs gb;
     DevBuf M;
-    std::vector<double> h;
     if (hipMalloc(&M.p, (size_t)N * N * 8) != hipSuccess) { snprintf(err, errlen, "hipMalloc of a %d x %d matrix failed", N, N); return SPG_ENOMEM; }
     HIPCHK(hipMemsetAsync(M.p, 0, (size_t)N * N * 8, s));
-    if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for dense assembly failed (%d)", rc); goto done; }
-    if (in.D == 6) launch_assemble<6>(gb, (double *)M.p, N, s);
-    else launch_assemble<3>(gb, (double *)M.p, N, s);
+    if (int rc = stage_graph(in, gb, s)) { snprintf(err, errlen, "staging the graph for dense assembly failed (%d)", rc); return rc; }
+    launch_assemble(in.D, gb, (double *)M.p, N, s);
     HIPCHK(hipGetLastError());
-    h.resize((size_t)N * N);
+    std::vector<double> h((size_t)N * N);
     HIPCHK(hipMemcpyAsync(h.data(), M.p, (size_t)N * N * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++) out[(size_t)i * n + j] = (j <= i) ? h[(size_t)i * N + j] : h[(size_t)j * N + i];
-done:
-    return rc;
+    return 0;
 }
 
 // GraphWrapperG2O::covariance() (src/graph_wrapper_g2o.cpp:368-373): info.llt().solve(I). Dense on the device:
@@ -1508,12 +1536,9 @@ done:
 // Sigma = Y Y^T with one triangular sweep of the tile kernel (K = N). Host output n x n row-major, full symmetric.
 int hip_dense_covariance(void *stream, const DenseGraphIn &in, int n, double *out, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
-    int rc = 0;
     const int N = round_up(std::max(n, 1)), nt = N / TB;
     GraphBufs gb;
     DevBuf M, Y, C, linv, linv_all, bad;
-    std::vector<double> h;
-    int h_bad = 0;
     if (hipMalloc(&M.p, (size_t)N * N * 8) != hipSuccess || hipMalloc(&Y.p, (size_t)N * N * 8) != hipSuccess ||
         hipMalloc(&C.p, (size_t)N * N * 8) != hipSuccess) {
         snprintf(err, errlen, "hipMalloc of three %d x %d matrices failed", N, N);
@@ -1526,28 +1551,25 @@ int hip_dense_covariance(void *stream, const DenseGraphIn &in, int n, double *ou
     HIPCHK(hipMemsetAsync(Y.p, 0, (size_t)N * N * 8, s));
     HIPCHK(hipMemsetAsync(C.p, 0, (size_t)N * N * 8, s));
     HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), s));
-    if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for dense assembly failed (%d)", rc); goto done; }
-    if (in.D == 6) launch_assemble<6>(gb, (double *)M.p, N, s);
-    else launch_assemble<3>(gb, (double *)M.p, N, s);
+    if (int rc = stage_graph(in, gb, s)) { snprintf(err, errlen, "staging the graph for dense assembly failed (%d)", rc); return rc; }
+    launch_assemble(in.D, gb, (double *)M.p, N, s);
     if (N > n) hipLaunchKernelGGL(pad_identity_kernel, dim3((N - n + 255) / 256), dim3(256), 0, s, (double *)M.p, N, n, N);
     hipLaunchKernelGGL(pad_identity_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (double *)Y.p, N, 0, N);
     potrf_lower((double *)M.p, N, (double *)linv.p, (int *)bad.p, s);
     rsolve_lower_transposed((double *)Y.p, N, (const double *)M.p, N, N, (double *)linv_all.p, (int *)bad.p, s);
-    {
-        TileOp yyt{(double *)C.p, (const double *)Y.p, (const double *)Y.p, (long long)TB * N, TB, (long long)TB * N, (long long)TB * N,
-                   N, N, N, nt, nt, 1, 0, N / KC};
-        launch_tiles(yyt, s);
-    }
+    TileOp yyt{(double *)C.p, (const double *)Y.p, (const double *)Y.p, (long long)TB * N, TB, (long long)TB * N, (long long)TB * N,
+               N, N, N, nt, nt, 1, 0, N / KC};
+    launch_tiles(yyt, s);
     HIPCHK(hipGetLastError());
-    h.resize((size_t)N * N);
+    std::vector<double> h((size_t)N * N);
+    int h_bad = 0;
     HIPCHK(hipMemcpyAsync(h.data(), C.p, (size_t)N * N * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (h_bad) { snprintf(err, errlen, "covariance: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
+    if (h_bad) { snprintf(err, errlen, "covariance: the information matrix is not positive definite"); return SPG_ENOTPD; }
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++) out[(size_t)i * n + j] = (j <= i) ? h[(size_t)i * N + j] : h[(size_t)j * N + i];
-done:
-    return rc;
+    return 0;
 }
 
 void hip_big_release_scratch() {
@@ -1563,8 +1585,9 @@ int hip_big_glc_dense(void *stream, const DenseGraphIn &in, int m, int k, int Nm
     if (flops) *flops = nm * nm * nm / 3.0 + nm * nm * n + nm * n * n + nr * nr * nr / 3.0 + nr * nr * nr / 3.0;
     static const bool trace = [] { const char *e = getenv("SPG_BIG_TRACE"); return e && e[0] == '1'; }();      // diagnostic: host time of a call next to its device time
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = in.D == 6 ? big_glc_dense_impl<6>((hipStream_t)stream, in, m, k, Nm, new_off, orec, n_new_max, tag, seconds, err, errlen)
-                             : big_glc_dense_impl<3>((hipStream_t)stream, in, m, k, Nm, new_off, orec, n_new_max, tag, seconds, err, errlen);
+    const int rc = by_dim(in.D, [&](auto d) {
+        return big_glc_dense_impl<decltype(d)::value>((hipStream_t)stream, in, m, k, Nm, new_off, orec, n_new_max, tag, seconds, err, errlen);
+    });
     if (trace) fprintf(stderr, "big blanket n=%d nm=%d: call %.3f ms, device %.3f ms\n", (int)n, (int)nm,
                        1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), seconds ? 1e3 * *seconds : 0.0);
     return rc;
@@ -1574,19 +1597,13 @@ int hip_big_glc_dense(void *stream, const DenseGraphIn &in, int m, int k, int Nm
 // kept block starting at Nm (multiple of 64); other.pos orders other's variables [kept | pad].
 // kept_vpo_*: pose offsets of the kept vertices in both arenas, in kept order.
 int hip_dense_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, int n_marg, int n_keep,
-                  const int64_t *kept_vpo_base, const int64_t *kept_vpo_other, double *terms, double *seconds,
-                  char *err, size_t errlen) {
+                  const int64_t *kept_vpo_base, const int64_t *kept_vpo_other, spg_kld_terms &out, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
-    int rc = 0;
     const int D = base.D, nk = n_keep / D;
     const int Nm = round_up(n_marg), Ng = round_up(std::max(n_keep, 1)), N = Nm + Ng, ntg = Ng / TB;
     GraphBufs gb, go;
     DevBuf Mb, X, Y, linv, linv_all, bad, partial, outb, diff, rowsq, vb, vo;
-    int h_bad[2] = {0, 0};
-    double h_out[4] = {0, 0, 0, 0};
     const int np = 1024;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
     if (hipMalloc(&Mb.p, (size_t)N * N * 8) != hipSuccess || hipMalloc(&X.p, (size_t)Ng * Ng * 8) != hipSuccess ||
         hipMalloc(&Y.p, (size_t)Ng * Ng * 8) != hipSuccess) {
         snprintf(err, errlen, "hipMalloc of the dense KLD matrices failed (N = %d, Ng = %d)", N, Ng);
@@ -1599,66 +1616,60 @@ int hip_dense_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &ot
     HIPCHK(hipMalloc(&outb.p, 4 * 8));
     HIPCHK(hipMalloc(&diff.p, (size_t)Ng * 8));
     HIPCHK(hipMalloc(&rowsq.p, (size_t)Ng * 8));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    EventTimer timer;
+    int rc;
     if ((rc = upload(vb, kept_vpo_base, (size_t)nk, s)) || (rc = upload(vo, kept_vpo_other, (size_t)nk, s)) ||
         (rc = stage_graph(base, gb, s)) || (rc = stage_graph(other, go, s))) {
         snprintf(err, errlen, "staging the graphs for the dense KLD failed (%d)", rc);
-        goto done;
+        return rc;
     }
-    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(timer.start(s));
     HIPCHK(hipMemsetAsync(Mb.p, 0, (size_t)N * N * 8, s));
     HIPCHK(hipMemsetAsync(X.p, 0, (size_t)Ng * Ng * 8, s));
     HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
     HIPCHK(hipMemsetAsync(diff.p, 0, (size_t)Ng * 8, s));
-    if (D == 6) { launch_assemble<6>(gb, (double *)Mb.p, N, s); launch_assemble<6>(go, (double *)X.p, Ng, s); }
-    else { launch_assemble<3>(gb, (double *)Mb.p, N, s); launch_assemble<3>(go, (double *)X.p, Ng, s); }
+    launch_assemble(D, gb, (double *)Mb.p, N, s);
+    launch_assemble(D, go, (double *)X.p, Ng, s);
     if (Nm > n_marg) hipLaunchKernelGGL(pad_identity_kernel, dim3((Nm - n_marg + 255) / 256), dim3(256), 0, s, (double *)Mb.p, N, n_marg, Nm);
     if (Ng > n_keep) {
         hipLaunchKernelGGL(pad_identity_kernel, dim3((Ng - n_keep + 255) / 256), dim3(256), 0, s, (double *)Mb.p, N, Nm + n_keep, N);
         hipLaunchKernelGGL(pad_identity_kernel, dim3((Ng - n_keep + 255) / 256), dim3(256), 0, s, (double *)X.p, Ng, n_keep, Ng);
     }
-    if (D == 6) hipLaunchKernelGGL((pose_diff_kernel<6>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, (double *)diff.p);
-    else hipLaunchKernelGGL((pose_diff_kernel<3>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, (double *)diff.p);
+    launch_pose_diff(D, s, base.dev_arena, (const int64_t *)vb.p, other.dev_arena, (const int64_t *)vo.p, nk, (double *)diff.p);
     potrf_lower((double *)Mb.p, N, (double *)linv.p, (int *)bad.p, s);
     potrf_lower((double *)X.p, Ng, (double *)linv.p, (int *)bad.p + 1, s);
-    {
-        const double *Ls = (const double *)Mb.p + ((long long)Nm * N + Nm);
-        hipLaunchKernelGGL(transpose_lower_kernel, dim3(Ng / 32, Ng / 32), dim3(256), 0, s, (const double *)X.p, Ng, (double *)Y.p, Ng, Ng);
-        // Mahalanobis and log-dets need Y = L_x^T before the solve overwrites it
-        hipLaunchKernelGGL(upper_matvec_sq_kernel, dim3(Ng / 4), dim3(256), 0, s, (const double *)Y.p, Ng, Ng, (const double *)diff.p, (double *)rowsq.p);
-        hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, (const double *)partial.p, 0, (const double *)X.p, Ng, Ls, N, Ng,
-                           (const double *)Y.p, Ng, (const double *)rowsq.p, (double *)outb.p);
-        HIPCHK(hipMemcpyAsync(h_out, outb.p, 4 * 8, hipMemcpyDeviceToHost, s));
-        rsolve_lower_transposed((double *)Y.p, Ng, Ls, N, Ng, (double *)linv_all.p, (int *)bad.p, s);
-        hipLaunchKernelGGL(sumsq_kernel, dim3(np), dim3(256), 0, s, (const double *)Y.p, Ng, Ng, (double *)partial.p);
-        hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, (const double *)partial.p, np, (const double *)X.p, Ng, Ls, N, 0,
-                           (const double *)Y.p, Ng, (const double *)nullptr, (double *)outb.p);
-    }
+    const double *Ls = (const double *)Mb.p + ((long long)Nm * N + Nm);
+    hipLaunchKernelGGL(transpose_lower_kernel, dim3(Ng / 32, Ng / 32), dim3(256), 0, s, (const double *)X.p, Ng, (double *)Y.p, Ng, Ng);
+    // Mahalanobis and log-dets need Y = L_x^T before the solve overwrites it
+    hipLaunchKernelGGL(upper_matvec_sq_kernel, dim3(Ng / 4), dim3(256), 0, s, (const double *)Y.p, Ng, Ng, (const double *)diff.p, (double *)rowsq.p);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, (const double *)partial.p, 0, (const double *)X.p, Ng, Ls, N, Ng,
+                       (const double *)Y.p, Ng, (const double *)rowsq.p, (double *)outb.p);
+    double h_out[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h_out, outb.p, 4 * 8, hipMemcpyDeviceToHost, s));
+    rsolve_lower_transposed((double *)Y.p, Ng, Ls, N, Ng, (double *)linv_all.p, (int *)bad.p, s);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(np), dim3(256), 0, s, (const double *)Y.p, Ng, Ng, (double *)partial.p);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, (const double *)partial.p, np, (const double *)X.p, Ng, Ls, N, 0,
+                       (const double *)Y.p, Ng, (const double *)nullptr, (double *)outb.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, s));
-    {
-        double h_sum[4];
-        HIPCHK(hipStreamSynchronize(s));   // h_out (first finish) is in place
-        double logdetx = h_out[1], logdet_s = h_out[2], mahal = h_out[3];
-        HIPCHK(hipMemcpy(h_sum, outb.p, 4 * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        if (h_bad[0] || h_bad[1]) {
-            snprintf(err, errlen, "global KLD: %s information matrix is not positive definite", h_bad[0] ? "the baseline" : "the sparsified");
-            rc = SPG_ENOTPD;
-            goto done;
-        }
-        const double innerprod = h_sum[0] - (double)(Ng - n_keep);   // the unit pad rows contribute 1 each
-        const double logdety = -logdet_s;                            // reference sign (mode InformationInformation)
-        terms[0] = 0.5 * (innerprod + mahal - logdetx - logdety - n_keep);
-        terms[1] = innerprod; terms[2] = mahal; terms[3] = logdetx; terms[4] = logdety; terms[5] = n_keep;
-        if (seconds) *seconds = 1e-3 * ms;
+    HIPCHK(timer.stop(s));
+    HIPCHK(hipStreamSynchronize(s));   // h_out (first finish) is in place
+    const double logdetx = h_out[1], logdet_s = h_out[2], mahal = h_out[3];
+    double h_sum[4];
+    int h_bad[2] = {0, 0};
+    float ms = 0;
+    HIPCHK(hipMemcpy(h_sum, outb.p, 4 * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(timer.ms(ms));
+    if (h_bad[0] || h_bad[1]) {
+        snprintf(err, errlen, "global KLD: %s information matrix is not positive definite", h_bad[0] ? "the baseline" : "the sparsified");
+        return SPG_ENOTPD;
     }
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    const double innerprod = h_sum[0] - (double)(Ng - n_keep);   // the unit pad rows contribute 1 each
+    const double logdety = -logdet_s;                            // reference sign (mode InformationInformation)
+    out.kld = 0.5 * (innerprod + mahal - logdetx - logdety - n_keep);
+    out.innerprod = innerprod; out.mahalanobis = mahal; out.logdetx = logdetx; out.logdety = logdety; out.n = n_keep;
+    out.device_seconds += 1e-3 * ms;
+    return 0;
 }
 
 // GraphWrapperG2O::optimize (src/graph_wrapper_g2o.cpp:250-269) = g2o Levenberg-Marquardt with one
@@ -1685,101 +1696,90 @@ struct LMLinear {
 
 // n: number of unknowns; nvec >= n: length of the vectors (b, sol)
 int lm_run(hipStream_t s, const spg::DenseGraphIn &in, GraphBufs &gb, int n, int nvec, int iterations, LMLinear &lin,
-           double *stats, double *seconds, char *err, size_t errlen) {
-    int rc = 0;
+           spg_optimize_stats &out, char *err, size_t errlen) {
     const int D = in.D, PS = (D == 6) ? 7 : 3;
     DevBuf bad, b, sol, chi, scal, backup;
-    double h_s[4] = {0, 0, 0, 0};
-    int h_bad = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
-    double lambda = 0, ni = 2, chi_first = 0, chi_last = 0;
-    int it = 0, trials = 0;
     HIPCHK(hipMalloc(&bad.p, sizeof(int)));
     HIPCHK(hipMalloc(&b.p, (size_t)nvec * 8));
     HIPCHK(hipMalloc(&sol.p, (size_t)nvec * 8));
     HIPCHK(hipMalloc(&chi.p, (size_t)std::max(in.ne, 1) * 8));
     HIPCHK(hipMalloc(&scal.p, 4 * 8));
     HIPCHK(hipMalloc(&backup.p, (size_t)std::max(in.nv, 1) * PS * 8));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, s));
-    {
-        double *arena = (double *)const_cast<void *>(in.dev_arena);
-        auto poses = [&](int mode) {
-            if (D == 6) hipLaunchKernelGGL((pose_update_kernel<6>), dim3((in.nv + 63) / 64), dim3(64), 0, s, arena, gb.dev.vpo, gb.dev.pos, in.nv, (const double *)sol.p, (double *)backup.p, mode);
-            else hipLaunchKernelGGL((pose_update_kernel<3>), dim3((in.nv + 63) / 64), dim3(64), 0, s, arena, gb.dev.vpo, gb.dev.pos, in.nv, (const double *)sol.p, (double *)backup.p, mode);
-        };
-        // chi2 of the current estimates into scal[slot] (the GLC kernel refreshes the weighted errors)
-        auto chi2_into = [&](int slot, bool refresh_glc) {
-            if (refresh_glc) {
-                if (D == 6) launch_glc_jacobians<6>(gb, s);
-                else launch_glc_jacobians<3>(gb, s);
-            }
-            if (in.ne > 0) {
-                if (D == 6) hipLaunchKernelGGL((edge_chi2_kernel<6>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (double *)chi.p);
-                else hipLaunchKernelGGL((edge_chi2_kernel<3>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (double *)chi.p);
-            }
-            hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)chi.p, in.ne, (double *)scal.p, slot);
-        };
-        bool terminate = false;
-        for (; it < iterations && !terminate; it++) {
-            // buildSystem: H, b and chi2 at the current estimates
-            HIPCHK(hipMemsetAsync(b.p, 0, (size_t)nvec * 8, s));
-            if ((rc = lin.build(s, gb, (double *)b.p, (double *)scal.p, err, errlen))) goto done;
-            chi2_into(0, false);
-            HIPCHK(hipMemcpyAsync(h_s, scal.p, 2 * 8, hipMemcpyDeviceToHost, s));
+    EventTimer timer;
+    HIPCHK(timer.start(s));
+    double *arena = (double *)const_cast<void *>(in.dev_arena);
+    auto poses = [&](int mode) {
+        by_dim(D, [&](auto d) {
+            hipLaunchKernelGGL((pose_update_kernel<decltype(d)::value>), dim3((in.nv + 63) / 64), dim3(64), 0, s, arena, gb.dev.vpo, gb.dev.pos, in.nv, (const double *)sol.p, (double *)backup.p, mode);
+        });
+    };
+    // chi2 of the current estimates into scal[slot] (the GLC kernel refreshes the weighted errors)
+    auto chi2_into = [&](int slot, bool refresh_glc) {
+        by_dim(D, [&](auto d) {
+            if (refresh_glc) launch_glc_jacobians<decltype(d)::value>(gb, s);
+            if (in.ne > 0) hipLaunchKernelGGL((edge_chi2_kernel<decltype(d)::value>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (double *)chi.p);
+        });
+        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)chi.p, in.ne, (double *)scal.p, slot);
+    };
+    double h_s[4] = {0, 0, 0, 0};
+    double lambda = 0, ni = 2, chi_first = 0, chi_last = 0;
+    int it = 0, trials = 0;
+    bool terminate = false;
+    for (; it < iterations && !terminate; it++) {
+        // buildSystem: H, b and chi2 at the current estimates
+        HIPCHK(hipMemsetAsync(b.p, 0, (size_t)nvec * 8, s));
+        if (int rc = lin.build(s, gb, (double *)b.p, (double *)scal.p, err, errlen)) return rc;
+        chi2_into(0, false);
+        HIPCHK(hipMemcpyAsync(h_s, scal.p, 2 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        double currentChi = h_s[0];
+        if (it == 0) { chi_first = currentChi; lambda = 1e-5 * h_s[1]; ni = 2; }
+        chi_last = currentChi;
+        double rho = 0;
+        int qmax = 0;
+        bool lambda_ok = true;
+        do {
+            poses(1);                                                        // push()
+            HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), s));
+            if (int rc = lin.solve(s, gb, lambda, (const double *)b.p, (double *)sol.p, (int *)bad.p, err, errlen)) return rc;
+            int h_bad = 0;
+            HIPCHK(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
-            double currentChi = h_s[0];
-            if (it == 0) { chi_first = currentChi; lambda = 1e-5 * h_s[1]; ni = 2; }
-            chi_last = currentChi;
-            double rho = 0;
-            int qmax = 0;
-            bool lambda_ok = true;
-            do {
-                poses(1);                                                        // push()
-                HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), s));
-                if ((rc = lin.solve(s, gb, lambda, (const double *)b.p, (double *)sol.p, (int *)bad.p, err, errlen))) goto done;
-                HIPCHK(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                const bool ok2 = h_bad == 0;
-                if (!ok2) HIPCHK(hipMemsetAsync(sol.p, 0, (size_t)nvec * 8, s));   // x = 0: the trial is rejected below
-                poses(0);                                                        // update(x)
-                chi2_into(2, true);
-                hipLaunchKernelGGL(lm_scale_kernel, dim3(1), dim3(256), 0, s, (const double *)sol.p, (const double *)b.p, n, lambda, (double *)scal.p, 3);
-                HIPCHK(hipMemcpyAsync(h_s, scal.p, 4 * 8, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                double tempChi = ok2 ? h_s[2] : std::numeric_limits<double>::max();
-                rho = (currentChi - tempChi) / (h_s[3] + 1e-3);
-                trials++;
-                if (rho > 0 && std::isfinite(tempChi)) {
-                    double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-                    alpha = std::min(alpha, 2.0 / 3.0);
-                    lambda *= std::max(1.0 / 3.0, alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    chi_last = tempChi;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    poses(2);                                                    // pop()
-                    if (!std::isfinite(lambda)) { lambda_ok = false; break; }
-                }
-                qmax++;
-            } while (rho < 0 && qmax < 10);
-            if (qmax == 10 || rho == 0 || !lambda_ok) terminate = true;
-        }
+            const bool ok2 = h_bad == 0;
+            if (!ok2) HIPCHK(hipMemsetAsync(sol.p, 0, (size_t)nvec * 8, s));   // x = 0: the trial is rejected below
+            poses(0);                                                        // update(x)
+            chi2_into(2, true);
+            hipLaunchKernelGGL(lm_scale_kernel, dim3(1), dim3(256), 0, s, (const double *)sol.p, (const double *)b.p, n, lambda, (double *)scal.p, 3);
+            HIPCHK(hipMemcpyAsync(h_s, scal.p, 4 * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            double tempChi = ok2 ? h_s[2] : std::numeric_limits<double>::max();
+            rho = (currentChi - tempChi) / (h_s[3] + 1e-3);
+            trials++;
+            if (rho > 0 && std::isfinite(tempChi)) {
+                double alpha = 1.0 - std::pow(2 * rho - 1, 3);
+                alpha = std::min(alpha, 2.0 / 3.0);
+                lambda *= std::max(1.0 / 3.0, alpha);
+                ni = 2;
+                currentChi = tempChi;
+                chi_last = tempChi;
+            } else {
+                lambda *= ni;
+                ni *= 2;
+                poses(2);                                                    // pop()
+                if (!std::isfinite(lambda)) { lambda_ok = false; break; }
+            }
+            qmax++;
+        } while (rho < 0 && qmax < 10);
+        if (qmax == 10 || rho == 0 || !lambda_ok) terminate = true;
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(timer.stop(s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    stats[0] = it; stats[1] = trials; stats[2] = chi_first; stats[3] = chi_last; stats[4] = lambda;
-    if (seconds) *seconds = 1e-3 * ms;
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    float ms = 0;
+    HIPCHK(timer.ms(ms));
+    out.iterations = it; out.trials = trials; out.chi2_initial = chi_first; out.chi2_final = chi_last; out.lambda_final = lambda;
+    out.device_seconds += 1e-3 * ms;
+    return 0;
 }
 
 // Dense linear algebra for LM: H and a working copy A in HBM, the blocked fp64-MFMA Cholesky, two blocked
@@ -1798,17 +1798,13 @@ struct DenseLM : LMLinear {
         return 0;
     }
     int build(hipStream_t s, const GraphBufs &gb, double *b, double *scal, char *err, size_t errlen) override {
-        int rc = 0;
         HIPCHK(hipMemsetAsync(H.p, 0, (size_t)N * N * 8, s));
-        if (D == 6) launch_assemble<6>(gb, (double *)H.p, N, s, b);
-        else launch_assemble<3>(gb, (double *)H.p, N, s, b);
+        launch_assemble(D, gb, (double *)H.p, N, s, b);
         if (N > n) hipLaunchKernelGGL(pad_identity_kernel, dim3((N - n + 255) / 256), dim3(256), 0, s, (double *)H.p, N, n, N);
         hipLaunchKernelGGL(max_diag_kernel, dim3(1), dim3(256), 0, s, (const double *)H.p, N, n, scal, 1);
-    done:
-        return rc;
+        return 0;
     }
     int solve(hipStream_t s, const GraphBufs &, double lambda, const double *b, double *sol, int *bad, char *err, size_t errlen) override {
-        int rc = 0;
         HIPCHK(hipMemcpyAsync(A.p, H.p, (size_t)N * N * 8, hipMemcpyDeviceToDevice, s));
         if (n > 0) hipLaunchKernelGGL(add_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (double *)A.p, N, n, lambda);
         potrf_lower((double *)A.p, N, (double *)linv.p, bad, s);
@@ -1819,8 +1815,7 @@ struct DenseLM : LMLinear {
         HIPCHK(hipMemcpyAsync(rhs.p, sol, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
         for (int j = nt - 1; j >= 0; j--)
             hipLaunchKernelGGL(trsv_backward_step, dim3(j + 1), dim3(64), 0, s, (const double *)A.p, N, (const double *)linv_all.p, (double *)rhs.p, sol, j);
-    done:
-        return rc;
+        return 0;
     }
 };
 
@@ -1828,15 +1823,14 @@ struct DenseLM : LMLinear {
 
 namespace spg {
 
-int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, double *stats, double *seconds,
-                       char *err, size_t errlen) {
+int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     GraphBufs gb;
     DenseLM lin;
     int rc = lin.init(in.D, n, err, errlen);
     if (rc) return rc;
     if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for the optimiser failed (%d)", rc); return rc; }
-    return lm_run(s, in, gb, n, lin.N, iterations, lin, stats, seconds, err, errlen);
+    return lm_run(s, in, gb, n, lin.N, iterations, lin, out, err, errlen);
 }
 
 }  // namespace spg

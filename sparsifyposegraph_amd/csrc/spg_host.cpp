@@ -16,317 +16,7 @@
 // both). Each round scans the pending list in the reference's order and selects a vertex only if it
 // commutes with every earlier vertex that is selected in this round or still deferred — a deferred
 // vertex is represented by a superset D(u) of every vertex its blanket can reach before its turn.
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <set>
-#include <string>
-#include <thread>
-#if defined(__linux__)
-#include <pthread.h>
-#include <sched.h>
-#endif
-#include <unistd.h>
-#include <unordered_map>
-#include <unordered_set>
-#include <vector>
-#include "../../include/spg.h"
-#include "spg_internal.h"
-#include "spg_sparse_plan.hpp"
-
-namespace {
-inline int pose_stride(int d) { return d == 3 ? 3 : 7; }
-inline int info_len(int d) { return d * (d + 1) / 2; }
-inline double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-}  // namespace
-
-// Host mirror of the arena: grows without value-initialising (the regions the device produces are
-// never read before they are downloaded), unlike std::vector<double>::resize.
-struct HostMirror {
-    double *p = nullptr;
-    size_t n = 0, cap = 0;
-    ~HostMirror() { free(p); }
-    HostMirror() {}
-    HostMirror(const HostMirror &) = delete;
-    HostMirror &operator=(const HostMirror &) = delete;
-    double *data() { return p; }
-    const double *data() const { return p; }
-    size_t size() const { return n; }
-    double &operator[](size_t i) { return p[i]; }
-    const double &operator[](size_t i) const { return p[i]; }
-    void resize(size_t m) {
-        if (m > cap) {
-            size_t nc = std::max(m, cap * 2);
-            p = (double *)realloc(p, nc * sizeof(double));
-            if (!p) abort();
-            cap = nc;
-        }
-        n = m;
-    }
-};
-
-// Small vector of trivially copyable T with N inline slots sharing their storage with the heap pointer of
-// the spilled form: sizeof == 8 + N*sizeof(T), so per-vertex adjacency (N = 6 edge ids) and owner lists
-// (N = 3 references) are one dense 32-byte record each instead of a vector header plus a heap chunk — the
-// scheduler and the graph update are bound by the cache misses on exactly these lists.
-template <class T, int N>
-struct InlVec {
-    int32_t n = 0, cap = N;
-    union { T inl[N]; T *ptr; };
-    InlVec() {}
-    InlVec(const InlVec &o) : n(o.n), cap(o.cap) {
-        if (cap > N) { ptr = (T *)malloc(sizeof(T) * (size_t)cap); memcpy(ptr, o.ptr, sizeof(T) * (size_t)n); }
-        else memcpy(inl, o.inl, sizeof inl);
-    }
-    InlVec(InlVec &&o) noexcept : n(o.n), cap(o.cap) {
-        if (cap > N) { ptr = o.ptr; o.cap = N; o.n = 0; }
-        else memcpy(inl, o.inl, sizeof inl);
-    }
-    InlVec &operator=(InlVec o) noexcept {
-        if (cap > N) free(ptr);
-        n = o.n; cap = o.cap;
-        if (cap > N) { ptr = o.ptr; o.cap = N; o.n = 0; }
-        else memcpy(inl, o.inl, sizeof inl);
-        return *this;
-    }
-    ~InlVec() { if (cap > N) free(ptr); }
-    T *data() { return cap > N ? ptr : inl; }
-    const T *data() const { return cap > N ? ptr : inl; }
-    T *begin() { return data(); }
-    T *end() { return data() + n; }
-    const T *begin() const { return data(); }
-    const T *end() const { return data() + n; }
-    size_t size() const { return (size_t)n; }
-    bool empty() const { return n == 0; }
-    T &operator[](size_t i) { return data()[i]; }
-    const T &operator[](size_t i) const { return data()[i]; }
-    T &back() { return data()[n - 1]; }
-    void pop_back() { n--; }
-    void clear() { n = 0; }
-    void push_back(const T &v) {
-        if (n == cap) {
-            int32_t nc = cap * 2;
-            T *p = (T *)malloc(sizeof(T) * (size_t)nc);
-            if (!p) abort();
-            memcpy(p, data(), sizeof(T) * (size_t)n);
-            if (cap > N) free(ptr);
-            ptr = p; cap = nc;
-        }
-        data()[n++] = v;
-    }
-};
-
-struct spg_ctx {
-    spg_backend be{};
-    bool is_hip = false;
-    int rank = 0, nranks = 1;
-    void *rccl = nullptr;         // communicator handle of csrc/spg_rccl.cpp (nullptr: single rank / no id given)
-    int tag_counter = 0;          // ready tags are unique per context (its mailboxes are shared by all graphs)
-    int linear_solver = 0;        // SPG_SOLVER_*: dense / block-sparse factorisation for optimize() and the global KLD
-    spg::StreamPort *sim_port = nullptr;   // tools/host_sim.cpp only: a simulated persistent worker behind an injected backend
-    char err[768] = {0};
-};
-
-// 32 bytes (two per cache line, never straddling one); a pose-pose edge carries its two endpoints inline (vtx[0],
-// vtx[1]) — the scheduler walks edges by the million and would otherwise take a second cache miss per edge for the
-// endpoint list; an n-ary GLC edge keeps its vertices in spg_graph::everts at index vtx[0].
-// `key` orders the edges of a blanket for the Hessian sum: the position the edge has in the REFERENCE's sequential
-// execution (insertion order; edges created by a removal come after everything that existed when the call began, in
-// removal-list order of their root, then in emission order) — the order g2o's edge set hands them out in the
-// sequential loop, and independent of the order in which this library happens to commit commuting removals.
-struct GEdge {
-    int64_t off;
-    int64_t key;
-    int32_t len;
-    int32_t vtx[2];
-    int16_t nv;
-    int8_t kind;
-    uint8_t alive;
-};
-
-struct RoundBlanket {
-    int32_t root;                 // vertex index
-    int32_t n_remove;
-    // flat pools (spg_graph::rb_verts / rb_edges) instead of per-blanket vectors: no allocation per blanket
-    int32_t vbeg = 0, nv = 0;     // vertex indices, removed first (asc id) then kept (asc id)
-    int32_t ebeg = 0, ne = 0;     // edge ids, ascending
-    int32_t rank = 0;
-    int32_t owner = -1;           // id in spg_graph::owners while the blanket is scheduled / in flight
-    spg_blanket_desc desc{};
-};
-
-struct BlanketLog { int32_t root_id, round, status, info; double kld, min_gap; };
-
-// One batch of mutually independent blankets: what used to be "the round". Two of them can be in
-// flight on the two launch slots of the backend (the host prepares / commits one while the device
-// computes the other).
-struct Batch {
-    std::vector<RoundBlanket> rb;
-    std::vector<int32_t> rb_verts, rb_edges;
-    std::vector<spg_blanket_desc> h_blk;
-    std::vector<int64_t> h_vpo;
-    std::vector<spg_edge_ref> h_er;
-    std::vector<int32_t> h_ev;
-    std::vector<int64_t> chunk_hdr;   // per rank: doubles of out records at the start of its chunk
-    spg_round_info rinfo{};
-    bool round_open = false;
-    bool used_mailbox = false;
-    int eff_ranks = 1, eff_rank = 0;   // ranks the batch is split over (1 = computed whole by every rank)
-    int slot = 0;
-    int seq = 0;                       // launch order
-    int round_no = 0;
-    int tag = 0;                       // ready tag of the launch (out record word [5])
-    double t_launch = 0;               // SPG_TRACE=1 diagnostics
-    // blankets committed from the mailbox before their KLD tail finished: (log index, mailbox offset)
-    std::vector<std::pair<int32_t, int64_t>> kld_pending;
-    // hand-over to the submission thread (pipelined driver): 0 while the batch's descriptors are being written and
-    // handed to the device, 1 once that is done (submit_rc = result); a commit waits for 1
-    alignas(64) std::atomic<int> submitted{1};
-    int submit_rc = 0;
-    char pad_[56];
-};
-
-struct OwnRefT { int32_t oid; uint32_t gen; };
-
-struct spg_graph {
-    spg_ctx *ctx = nullptr;
-    int d = 0, ps = 0, rec = 0;
-    std::vector<int32_t> vid;
-    std::unordered_map<int32_t, int32_t> vidx;
-    // direct id -> index table next to the hash map, kept while the ids are small non-negative integers (g2o files number
-    // their vertices 0, 1, 2, ...): the 50 000 lookups of a removal list cost 2 ms of a 19 ms marginalisation through the map
-    std::vector<int32_t> vdirect;
-    bool vdirect_ok = true;
-    int32_t index_of(int32_t id) const {
-        if (vdirect_ok) return (id >= 0 && (size_t)id < vdirect.size()) ? vdirect[(size_t)id] : -1;
-        auto it = vidx.find(id);
-        return it == vidx.end() ? -1 : it->second;
-    }
-    std::vector<uint8_t> valive;
-    std::vector<int64_t> vpose;
-    // Per vertex, two cache lines. Line 0: adjacency — live edge ids, each with the far endpoint of a pose-pose edge
-    // (-1 for an n-ary edge), so that walking a neighbourhood reads no edge records. Line 1: the streaming driver's
-    // state of the vertex and what a hand-over needs of it (copies of vid[] / vpose[]).
-    struct AdjEnt { int32_t eid, other; operator int32_t() const { return eid; } };
-    struct SVtx {                                     // 24 bytes
-        int32_t nown;                                 // registered blankets (in flight or reserved) that contain the vertex: own[0 .. nown)
-        int32_t own[4];
-        int32_t slot;                                 // SV_STABLE / SV_INFLIGHT: the slot that holds the vertex's blanket
-    };
-    struct alignas(64) VRec {
-        InlVec<AdjEnt, 7> adj;
-        SVtx s;
-        int32_t id, pad_;
-        int64_t pose;
-        char spare_[24];
-        VRec() { s.nown = 0; s.slot = -1; id = 0; pad_ = 0; pose = 0; }
-    };
-    std::vector<VRec> vr;
-    std::vector<InlVec<struct OwnRefT, 3>> vown;      // batch scheduler: owners whose vertex set holds the vertex
-    // list position and state of every vertex in one small array (4 bytes per vertex: it stays in L2 while the per-vertex
-    // records stream through): -1 = not in the removal list of the running call, else (position << 2) | SV_*
-    std::vector<int32_t> cst;
-    std::vector<GEdge> edges;
-    std::vector<int32_t> everts;
-    int n_live_v = 0, n_live_e = 0;
-    // arena
-    void *dev = nullptr;
-    int64_t cap = 0, used = 0;
-    HostMirror host;               // mirror of [0, used)
-    int64_t dev_synced = 0;        // device holds [0, dev_synced)
-    int64_t stale_lo = 0, stale_hi = 0;  // host mirror range that only the device holds
-    // marginalisation state
-    bool active = false;
-    spg_options opts{};
-    int rank = 0, nranks = 1;
-    std::vector<int32_t> pending;   // removal list (vertex indices) in the caller's order; [pend_head, end) is still to do
-    size_t pend_head = 0;
-    std::vector<uint8_t> in_set;   // vertex index is in the removal list
-    static constexpr int NB = 8;                      // batches that can be in flight (= backend launch slots)
-    Batch bt[NB];
-    Batch *B = &bt[0];                                // batch the round functions currently work on
-    // Owner registry of the scheduler: every scheduled-but-uncommitted blanket and every vertex deferred
-    // in the current scheduling pass "owns" a vertex set; vowners[x] lists the owners whose set holds x.
-    // Blanket owners persist from the pass that selected them until their batch commits; entries die
-    // lazily: freeing an owner bumps its generation and stale references are dropped when next seen.
-    struct Owner { int32_t batch, off, len; uint32_t gen; };   // batch >= 0: bt[batch].rb_verts[off, off+len); -1: Dpool
-    using OwnRef = OwnRefT;
-    std::vector<Owner> owners;
-    std::vector<int32_t> owner_free, transient;       // free ids; deferred-vertex owners of the last pass
-    std::vector<int32_t> Dpool;                       // sets of the deferred-vertex owners, flat
-    int shard_threshold = -1;                         // < 0: cost model (shard_pays); >= 0: minimum blankets
-    int round_no = 0, launch_seq = 0;
-    bool pipelined = false;                           // two batches in flight (single rank, backend with slots)
-    spg_marg_stats stats{};
-    double tr_age = 0, tr_wait = 0, tr_first = 0; long tr_n = 0;   // SPG_TRACE=1: launch->commit-start, wait inside commit, launch->first ready word
-    std::vector<BlanketLog> log;
-    std::vector<double> hdr_buf;
-    // Submission thread of the pipelined driver: the graph thread selects and commits, this one writes the descriptors
-    // of a selected batch and hands it to the device (descriptor work + device hand-over are ~25 % of the host time per
-    // batch and need nothing the graph thread mutates: poses, edge records' locations and the batch's own lists)
-    // (every word the two threads exchange sits on its own cache line: the submission thread polls sub_tail, and a line
-    //  shared with anything the graph thread writes per blanket would bounce between the cores all the time)
-    std::thread sub_thread;
-    static constexpr uint32_t SUBQ = 8;
-    bool sub_active = false;
-    struct alignas(64) SubShared {
-        alignas(64) std::atomic<uint32_t> tail{0};    // written by the graph thread
-        alignas(64) Batch *q[SUBQ] = {nullptr};       // written by the graph thread
-        alignas(64) std::atomic<uint32_t> head{0};    // written by the submission thread
-        alignas(64) double seconds = 0;               // submission thread only: time spent (descriptors + hand-over)
-        alignas(64) std::atomic<bool> run{false};
-        char pad_[64];
-    } sub;
-    std::vector<int32_t> live_rank;                   // edge id -> index among live edges (spg_graph_vertex_edges)
-    long n_mutations = 0, live_rank_stamp = -1;       // bumped whenever an edge is added or dies
-    // canonical edge keys (GEdge::key): next key for an edge added by the caller; base of the running marginalisation
-    // (new edge e of the removal at list position p gets key_base + p * kKeyStride + e)
-    int64_t next_key = 0, key_base = 0;
-    static constexpr int64_t kKeyStride = 65536;
-    std::vector<int32_t> lpos;                        // vertex index -> position in the removal list of the running call, -1 otherwise
-    // scheduler scratch
-    std::vector<int32_t> vstamp, estamp;
-    int32_t stamp = 0;
-    std::vector<int32_t> ocnt;
-    std::vector<int32_t> lidx;
-    std::vector<int32_t> s_newpending, s_B, s_centres, s_Dv, s_tmp, s_work, s_seen, s_hit, s_vix;
-    std::vector<double> s_cost;
-    std::vector<int> s_first;
-    std::vector<int64_t> s_chunk_len;
-    // ---- streaming driver (stream_marginalize below): per-vertex / per-slot / per-position state, kept between calls
-    static constexpr int kSOwn = 4, kSMaxV = 16, kSMaxE = 44;
-    struct SSlot {                                    // one blanket in flight
-        int32_t pos, root, nv, ne, n_new_max, tag, logi, bell;
-        int32_t launched;                             // 0: a reservation (the blanket of a waiting entry), 1: in flight
-        int32_t npend, pend[3];                       // the blanket's other vertices that are list entries (-1: more than 3, look at all)
-        int32_t mcell;                                // its mailbox cell: cells are handed out in launch order, so the host polls and reads sequential memory
-        int64_t new_off, out_off;                     // out_off: emulated port only (out record in the arena), else -1
-        int32_t verts[kSMaxV];                        // removed vertex first, kept ones in ascending id
-        int32_t edges[kSMaxE];                        // ascending key
-    };
-    std::vector<SSlot> sslots;
-    std::vector<int32_t> s_free, s_fifo, s_fin, s_woken, s_ready, wl_next, wl_stable, wl_done;
-    int64_t unsorted_from = -1;                       // edges[unsorted_from ..) were appended in commit order by the streaming driver: see canonicalize_edge_order
-    bool layout_diverged = false;                     // the graph has streamed on one of several ranks: its arena layout is rank-specific, never shard it again
-    int stream_emulation = -1;                        // tests (spg_graph_set_stream_emulation): >= 0 = completion-order seed
-    int stream_disabled = 0;                          // SPG_STREAM=0 or spg_graph_set_stream_emulation(g, -2)
-};
-
-static inline const int32_t *edge_verts(const spg_graph *g, const GEdge &e) {
-    return e.nv == 2 ? e.vtx : g->everts.data() + e.vtx[0];
-}
-
-static int set_err(spg_ctx *c, int code, const char *fmt, const char *a = "") {
-    if (c) snprintf(c->err, sizeof c->err, fmt, a);
-    return code;
-}
+#include "spg_graph_impl.h"
 
 // ================================================================================= context
 // SPG_SEGV_BACKTRACE=1 (diagnostic): a SIGSEGV inside the process prints the native frames (addresses relative to the
@@ -509,7 +199,7 @@ extern "C" int spg_decimate_global(int last, int endvert, int sparsity, int, int
 // ================================================================================= arena
 static int arena_ensure(spg_graph *g, int64_t need);
 
-static int sync_host(spg_graph *g) {  // pull device-only ranges into the host mirror
+int sync_host(spg_graph *g) {  // pull device-only ranges into the host mirror
     if (g->stale_hi > g->stale_lo) {
         if ((int64_t)g->host.size() < g->used) g->host.resize((size_t)g->used);
         int rc = g->ctx->be.download(g->ctx->be.user, g->host.data() + g->stale_lo,
@@ -520,7 +210,7 @@ static int sync_host(spg_graph *g) {  // pull device-only ranges into the host m
     return 0;
 }
 
-static int sync_device(spg_graph *g) {  // push host-only tail to the device
+int sync_device(spg_graph *g) {  // push host-only tail to the device
     if (g->dev_synced < g->used) {
         if (int rc = arena_ensure(g, g->used)) return rc;
         int64_t lo = g->dev_synced;
@@ -690,7 +380,7 @@ extern "C" int spg_graph_num_edges(const spg_graph *g) { return g ? g->n_live_e 
 // would have inserted the edges in — so that two runs on the same input hand out byte-identical graphs. Lazy: it costs
 // ~3 ms on the 100k-pose graph and a marginalisation that is only followed by another one never pays it.
 static void next_stamp(spg_graph *g);
-static void canonicalize_edge_order(spg_graph *g) {
+void canonicalize_edge_order(spg_graph *g) {
     if (g->unsorted_from < 0 || g->active) return;
     const size_t from = (size_t)g->unsorted_from, n = g->edges.size() - from;
     g->unsorted_from = -1;
@@ -3312,551 +3002,5 @@ extern "C" int spg_graph_substitute_edge(spg_graph *g, const int32_t *marginaliz
     for (int i = 0; i < d; i++) for (int j = i; j < d; j++) info_upper[q++] = 0.5 * (cov[(size_t)i * d + j] + cov[(size_t)j * d + i]);
     for (int i = 0; i < ps; i++) meas[i] = acc[i];
     if (new_is_from) *to = g->vid[hit]; else *from = g->vid[hit];
-    return 0;
-}
-
-// ================================================================================= global KLD (a18)
-namespace {
-struct DenseStage {
-    std::vector<int32_t> pos, rowptr, inc, ev;
-    std::vector<spg_edge_ref> er;
-    spg::DenseGraphIn in;
-};
-
-// Live vertex indices in ascending id order.
-std::vector<int32_t> live_vertices_by_id(const spg_graph *g) {
-    std::vector<int32_t> v;
-    for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) v.push_back((int32_t)i);
-    std::sort(v.begin(), v.end(), [&](int32_t a, int32_t b) { return g->vid[a] < g->vid[b]; });
-    return v;
-}
-
-// st.pos must be filled (size = number of vertex slots, -1 = not a variable).
-void build_dense_stage(spg_graph *g, DenseStage &st) {
-    canonicalize_edge_order(g);
-    const int nv = (int)g->vid.size();
-    std::vector<int32_t> remap(g->edges.size(), -1);
-    for (size_t e = 0; e < g->edges.size(); e++) {
-        const GEdge &ge = g->edges[e];
-        if (!ge.alive) continue;
-        remap[e] = (int32_t)st.er.size();
-        st.er.push_back({ge.off, ge.len, ge.kind, (int32_t)st.ev.size(), ge.nv});
-        for (int i = 0; i < ge.nv; i++) st.ev.push_back(edge_verts(g, ge)[i]);
-    }
-    st.rowptr.assign((size_t)nv + 1, 0);
-    for (int v = 0; v < nv; v++) {
-        if (g->valive[v]) {
-            std::vector<int32_t> es;
-            for (int32_t e : g->vr[v].adj) if (remap[e] >= 0) es.push_back(remap[e]);
-            std::sort(es.begin(), es.end());
-            es.erase(std::unique(es.begin(), es.end()), es.end());
-            st.inc.insert(st.inc.end(), es.begin(), es.end());
-        }
-        st.rowptr[v + 1] = (int32_t)st.inc.size();
-    }
-    st.in.D = g->d; st.in.nv = nv; st.in.ne = (int)st.er.size();
-    st.in.pos = st.pos.data(); st.in.vpo = g->vpose.data(); st.in.rowptr = st.rowptr.data(); st.in.inc = st.inc.data();
-    st.in.er = st.er.data(); st.in.ev = st.ev.data(); st.in.n_ev = (int64_t)st.ev.size(); st.in.dev_arena = g->dev;
-}
-
-int resolve_fixed(const spg_graph *g, const std::vector<int32_t> &order, int32_t fixed_id) {
-    if (order.empty()) return -1;
-    if (fixed_id < 0) return order[0];   // the reference skips its first (smallest-id) vertex
-    auto it = g->vidx.find(fixed_id);
-    if (it == g->vidx.end() || !g->valive[it->second]) return -1;
-    return it->second;
-}
-}  // namespace
-
-extern "C" int64_t spg_graph_information(spg_graph *g, int32_t fixed_id, double *out, int64_t cap) {
-    if (!g || g->active) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_information: the fixed vertex is not in the graph");
-    const int64_t n = (int64_t)g->d * ((int64_t)order.size() - 1);
-    if (!out || cap < n * n) return n;
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_information needs the HIP backend");
-    if (int rc = sync_device(g)) return rc;
-    if (int rc = g->ctx->be.synchronize(g->ctx->be.user)) return rc;
-    DenseStage st;
-    st.pos.assign(g->vid.size(), -1);
-    int p = 0;
-    for (int32_t v : order) if (v != fixed) { st.pos[v] = p; p += g->d; }
-    build_dense_stage(g, st);
-    g->ctx->err[0] = 0;
-    int rc = spg::hip_dense_information(spg::hip_backend_stream(&g->ctx->be), st.in, (int)n, out, g->ctx->err, sizeof g->ctx->err);
-    return rc ? rc : n;
-}
-
-extern "C" int64_t spg_graph_covariance(spg_graph *g, int32_t fixed_id, double *out, int64_t cap) {
-    if (!g || g->active) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_covariance: the fixed vertex is not in the graph");
-    const int64_t n = (int64_t)g->d * ((int64_t)order.size() - 1);
-    if (!out || cap < n * n) return n;
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_covariance needs the HIP backend");
-    if (n > 46000) return set_err(g->ctx, SPG_ECAPACITY, "spg_graph_covariance: dense formulation limited to 46k variables");
-    if (int rc = sync_device(g)) return rc;
-    if (int rc = g->ctx->be.synchronize(g->ctx->be.user)) return rc;
-    DenseStage st;
-    st.pos.assign(g->vid.size(), -1);
-    int p = 0;
-    for (int32_t v : order) if (v != fixed) { st.pos[v] = p; p += g->d; }
-    build_dense_stage(g, st);
-    g->ctx->err[0] = 0;
-    int rc = spg::hip_dense_covariance(spg::hip_backend_stream(&g->ctx->be), st.in, (int)n, out, g->ctx->err, sizeof g->ctx->err);
-    return rc ? rc : n;
-}
-
-extern "C" int spg_graph_kullback_leibler(spg_graph *base, spg_graph *other, int32_t fixed_id, spg_kld_terms *out) {
-    if (!base || !other || !out || base->active || other->active) return SPG_EINVAL;
-    spg_ctx *ctx = base->ctx;
-    if (base->d != other->d) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: pose dimensions differ");
-    if (!ctx->is_hip || !other->ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_kullback_leibler needs the HIP backend");
-    if (spg::hip_backend_device(&ctx->be) != spg::hip_backend_device(&other->ctx->be))
-        return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: both graphs must live on the same device");
-    const int d = base->d;
-    std::vector<int32_t> ob = live_vertices_by_id(base), oo = live_vertices_by_id(other);
-    int fb = resolve_fixed(base, ob, fixed_id);
-    if (fb < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the fixed vertex is not in the baseline");
-    const int32_t fid = base->vid[fb];
-    int fo = resolve_fixed(other, oo, fid);
-    if (fo < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the fixed vertex is not in the sparsified graph");
-    // computeIndices (src/graph_wrapper_g2o.cpp:472-499): merge of the two id-sorted vertex lists
-    std::vector<int32_t> kept_b, kept_o, marg_b;
-    {
-        size_t j = 0;
-        for (int32_t v : ob) {
-            if (v == fb) continue;
-            while (j < oo.size() && (oo[j] == fo || other->vid[oo[j]] < base->vid[v])) {
-                if (oo[j] != fo) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the sparsified graph holds a vertex the baseline lacks");
-                j++;
-            }
-            if (j < oo.size() && other->vid[oo[j]] == base->vid[v]) { kept_b.push_back(v); kept_o.push_back(oo[j]); j++; }
-            else marg_b.push_back(v);
-        }
-        for (; j < oo.size(); j++)
-            if (oo[j] != fo) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the sparsified graph holds a vertex the baseline lacks");
-    }
-    if (kept_b.empty()) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: no common free vertex");
-    const int64_t n_marg = (int64_t)d * marg_b.size(), n_keep = (int64_t)d * kept_b.size();
-    const int64_t Nm = (n_marg + 63) / 64 * 64, Ng = (n_keep + 63) / 64 * 64;
-    const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && Nm + Ng > 46000);
-    if (!sparse && Nm + Ng > 46000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_kullback_leibler: dense formulation limited to 46k variables (16 GB)");
-    if (int rc = sync_device(base)) return rc;
-    if (int rc = sync_device(other)) return rc;
-    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
-    if (other->ctx != ctx) if (int rc = other->ctx->be.synchronize(other->ctx->be.user)) return rc;
-    if (sparse) {
-        // block-sparse multifrontal path: positions only number the blocks, the elimination order is the plan's
-        DenseStage sb, so;
-        sb.pos.assign(base->vid.size(), -1);
-        so.pos.assign(other->vid.size(), -1);
-        std::vector<uint8_t> is_marg(base->vid.size(), 0);
-        std::vector<int64_t> kvb, kvo;
-        int p = 0;
-        for (int32_t v : ob) if (v != fb) sb.pos[v] = p++;
-        for (int32_t v : marg_b) is_marg[v] = 1;
-        p = 0;
-        for (size_t i = 0; i < kept_b.size(); i++) {
-            so.pos[kept_o[i]] = p++;
-            kvb.push_back(base->vpose[kept_b[i]]);
-            kvo.push_back(other->vpose[kept_o[i]]);
-        }
-        build_dense_stage(base, sb);
-        build_dense_stage(other, so);
-        double terms[6] = {0, 0, 0, 0, 0, 0}, secs = 0, info[4] = {0, 0, 0, 0};
-        ctx->err[0] = 0;
-        int rc = spg::hip_sparse_kld(spg::hip_backend_stream(&ctx->be), sb.in, so.in, is_marg.data(), kept_b.data(), kept_o.data(), (int)kept_b.size(),
-                                     kvb.data(), kvo.data(), terms, &secs, info, ctx->err, sizeof ctx->err);
-        if (rc) return rc;
-        out->kld = terms[0]; out->innerprod = terms[1]; out->mahalanobis = terms[2]; out->logdetx = terms[3];
-        out->logdety = terms[4]; out->n = (int64_t)terms[5]; out->n_marginalized = n_marg; out->device_seconds = secs;
-        out->solver = SPG_SOLVER_SPARSE; out->supernodes = (int32_t)info[0]; out->front_bytes = info[2]; out->factor_flops = info[3];
-        return 0;
-    }
-    DenseStage sb, so;
-    sb.pos.assign(base->vid.size(), -1);
-    so.pos.assign(other->vid.size(), -1);
-    std::vector<int64_t> kvb, kvo;
-    {
-        int p = 0;
-        for (int32_t v : marg_b) { sb.pos[v] = p; p += d; }
-        p = (int)Nm;
-        int q = 0;
-        for (size_t i = 0; i < kept_b.size(); i++) {
-            sb.pos[kept_b[i]] = p; p += d;
-            so.pos[kept_o[i]] = q; q += d;
-            kvb.push_back(base->vpose[kept_b[i]]);
-            kvo.push_back(other->vpose[kept_o[i]]);
-        }
-    }
-    build_dense_stage(base, sb);
-    build_dense_stage(other, so);
-    double terms[6] = {0, 0, 0, 0, 0, 0}, secs = 0;
-    ctx->err[0] = 0;
-    int rc = spg::hip_dense_kld(spg::hip_backend_stream(&ctx->be), sb.in, so.in, (int)n_marg, (int)n_keep, kvb.data(), kvo.data(),
-                                terms, &secs, ctx->err, sizeof ctx->err);
-    if (rc) return rc;
-    out->kld = terms[0]; out->innerprod = terms[1]; out->mahalanobis = terms[2]; out->logdetx = terms[3];
-    out->logdety = terms[4]; out->n = (int64_t)terms[5]; out->n_marginalized = n_marg; out->device_seconds = secs;
-    out->solver = SPG_SOLVER_DENSE; out->supernodes = 0; out->front_bytes = 0; out->factor_flops = 0;
-    return 0;
-}
-
-// ================================================================================= covariance blocks (sparse factor)
-namespace {
-int live_index(const spg_graph *g, int32_t id) {
-    auto it = g->vidx.find(id);
-    return (it == g->vidx.end() || !g->valive[it->second]) ? -1 : it->second;
-}
-bool share_live_edge(const spg_graph *g, int32_t a, int32_t b) {
-    for (int32_t e : g->vr[a].adj) {
-        const GEdge &ge = g->edges[e];
-        if (!ge.alive) continue;
-        const int32_t *vs = edge_verts(g, ge);
-        for (int i = 0; i < ge.nv; i++) if (vs[i] == b) return true;
-    }
-    return false;
-}
-// every live vertex but the fixed one is a block, numbered by ascending id
-void stage_free_vertices(spg_graph *g, const std::vector<int32_t> &order, int fixed, DenseStage &st) {
-    st.pos.assign(g->vid.size(), -1);
-    int p = 0;
-    for (int32_t v : order) if (v != fixed) st.pos[v] = p++;
-    build_dense_stage(g, st);
-}
-void put_cov_stats(spg_cov_stats *st, double secs, const double *info) {
-    if (!st) return;
-    st->device_seconds = secs; st->supernodes = (int32_t)info[0]; st->front_bytes = info[1];
-    st->factor_flops = info[2]; st->selinv_flops = info[3];
-}
-// K vertex indices per request (-1 = the fixed vertex) -> (K D)^2 doubles per request
-int64_t cov_blocks(spg_graph *g, int fixed, const std::vector<int32_t> &order, int K, std::vector<int32_t> &req, double *out,
-                   spg_cov_stats *stats, const char *what) {
-    spg_ctx *ctx = g->ctx;
-    const int64_t n = (int64_t)req.size() / K, W = (int64_t)K * g->d, need = n * W * W;
-    if (!ctx->is_hip) {
-        snprintf(ctx->err, sizeof ctx->err, "%s needs the HIP backend", what);
-        return SPG_ESTATE;
-    }
-    for (int32_t &v : req) if (v == fixed) v = -1;
-    double secs = 0, info[4] = {0, 0, 0, 0};
-    if (n == 0 || order.size() < 2) {   // nothing but the fixed vertex: every block is zero
-        std::fill(out, out + need, 0.0);
-        put_cov_stats(stats, secs, info);
-        return need;
-    }
-    if (int rc = sync_device(g)) return rc;
-    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
-    DenseStage st;
-    stage_free_vertices(g, order, fixed, st);
-    ctx->err[0] = 0;
-    int rc = spg::hip_sparse_cov_blocks(spg::hip_backend_stream(&ctx->be), st.in, K, req.data(), (int)n, out, &secs, info, ctx->err, sizeof ctx->err);
-    if (rc) return rc;
-    put_cov_stats(stats, secs, info);
-    return need;
-}
-}  // namespace
-
-extern "C" int64_t spg_graph_marginal_covariances(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
-                                                  spg_cov_stats *stats) {
-    if (!g || g->active || (ids && n < 0)) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    const int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_marginal_covariances: the fixed vertex is not in the graph");
-    std::vector<int32_t> req;
-    if (!ids) req = order;
-    else {
-        req.resize((size_t)n);
-        for (int i = 0; i < n; i++) {
-            req[i] = live_index(g, ids[i]);
-            if (req[i] < 0) {
-                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_marginal_covariances: vertex %d is not in the graph", (int)ids[i]);
-                return SPG_EINVAL;
-            }
-        }
-    }
-    const int64_t need = (int64_t)req.size() * g->d * g->d;
-    if (!out || cap < need) return need;
-    return cov_blocks(g, fixed, order, 1, req, out, stats, "spg_graph_marginal_covariances");
-}
-
-extern "C" int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
-                                               spg_cov_stats *stats) {
-    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    const int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_covariances: the fixed vertex is not in the graph");
-    std::vector<int32_t> req((size_t)2 * n);
-    for (int i = 0; i < n; i++) {
-        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
-        const int va = live_index(g, a), vb = live_index(g, b);
-        const char *why = (va < 0 || vb < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same"
-                          : !share_live_edge(g, va, vb) ? "the vertices share no live edge" : nullptr;
-        if (why) {
-            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
-            return SPG_EINVAL;
-        }
-        req[2 * i] = va;
-        req[2 * i + 1] = vb;
-    }
-    const int64_t W = 2 * g->d, need = (int64_t)n * W * W;
-    if (!out || cap < need) return need;
-    return cov_blocks(g, fixed, order, 2, req, out, stats, "spg_graph_joint_covariances");
-}
-
-extern "C" int spg_graph_marginal_kld(spg_graph *base, spg_graph *other, int32_t fixed_id, int32_t *ids, double *kld, int cap,
-                                      spg_cov_stats *stats) {
-    if (!base || !other || base->active || other->active) return SPG_EINVAL;
-    spg_ctx *ctx = base->ctx;
-    if (base->d != other->d) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: pose dimensions differ");
-    std::vector<int32_t> ob = live_vertices_by_id(base), oo = live_vertices_by_id(other);
-    const int fb = resolve_fixed(base, ob, fixed_id);
-    if (fb < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the baseline");
-    const int fo = resolve_fixed(other, oo, base->vid[fb]);
-    if (fo < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the sparsified graph");
-    std::vector<int32_t> vb, vo, out_ids;
-    for (int32_t v : oo) {
-        if (v == fo) continue;
-        const int u = live_index(base, other->vid[v]);
-        if (u < 0) {
-            snprintf(ctx->err, sizeof ctx->err, "spg_graph_marginal_kld: the sparsified graph holds vertex %d, which the baseline lacks", (int)other->vid[v]);
-            return SPG_EINVAL;
-        }
-        vb.push_back(u);
-        vo.push_back(v);
-        out_ids.push_back(other->vid[v]);
-    }
-    const int nk = (int)vo.size();
-    if (!ids || !kld || cap < nk) return nk;
-    if (!ctx->is_hip || !other->ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_marginal_kld needs the HIP backend");
-    if (spg::hip_backend_device(&ctx->be) != spg::hip_backend_device(&other->ctx->be))
-        return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: both graphs must live on the same device");
-    double secs = 0, info[4] = {0, 0, 0, 0};
-    if (nk > 0) {
-        if (int rc = sync_device(base)) return rc;
-        if (int rc = sync_device(other)) return rc;
-        if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
-        if (other->ctx != ctx) if (int rc = other->ctx->be.synchronize(other->ctx->be.user)) return rc;
-        DenseStage sb, so;
-        stage_free_vertices(base, ob, fb, sb);
-        stage_free_vertices(other, oo, fo, so);
-        std::vector<int64_t> kvb, kvo;
-        for (int i = 0; i < nk; i++) { kvb.push_back(base->vpose[vb[i]]); kvo.push_back(other->vpose[vo[i]]); }
-        ctx->err[0] = 0;
-        int rc = spg::hip_sparse_marginal_kld(spg::hip_backend_stream(&ctx->be), sb.in, so.in, vb.data(), vo.data(), nk, kvb.data(), kvo.data(),
-                                              kld, &secs, info, ctx->err, sizeof ctx->err);
-        if (rc) return rc;
-    }
-    std::copy(out_ids.begin(), out_ids.end(), ids);
-    put_cov_stats(stats, secs, info);
-    return nk;
-}
-
-// ================================================================================= covariance of arbitrary pairs / sets
-namespace {
-void put_cov_solve_stats(spg_cov_solve_stats *st, double secs, const double *info) {
-    if (!st) return;
-    put_cov_stats(&st->cov, secs, info);
-    st->columns = (int32_t)info[4]; st->rhs_batches = (int32_t)info[5];
-    st->solve_flops = info[6]; st->solve_seconds = info[7];
-}
-// D x D sub-blocks Sigma(va[i], vb[i]) (vertex indices) at out + dst[i], row stride ld
-int64_t cov_solve(spg_graph *g, int fixed, const std::vector<int32_t> &order, std::vector<int32_t> &va, std::vector<int32_t> &vb,
-                  const std::vector<int64_t> &dst, int32_t ld, int64_t need, double *out, spg_cov_solve_stats *stats, const char *what) {
-    spg_ctx *ctx = g->ctx;
-    if (!ctx->is_hip) {
-        snprintf(ctx->err, sizeof ctx->err, "%s needs the HIP backend", what);
-        return SPG_ESTATE;
-    }
-    for (int32_t &v : va) if (v == fixed) v = -1;
-    for (int32_t &v : vb) if (v == fixed) v = -1;
-    double secs = 0, info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (need == 0 || order.size() < 2) {   // nothing but the fixed vertex: every block is zero
-        std::fill(out, out + need, 0.0);
-        put_cov_solve_stats(stats, secs, info);
-        return need;
-    }
-    if (int rc = sync_device(g)) return rc;
-    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
-    DenseStage st;
-    stage_free_vertices(g, order, fixed, st);
-    ctx->err[0] = 0;
-    int rc = spg::hip_sparse_cov_solve(spg::hip_backend_stream(&ctx->be), st.in, va.data(), vb.data(), dst.data(), ld, (int64_t)va.size(), need, out,
-                                       &secs, info, ctx->err, sizeof ctx->err);
-    if (rc) return rc;
-    put_cov_solve_stats(stats, secs, info);
-    return need;
-}
-}  // namespace
-
-extern "C" int64_t spg_graph_pair_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
-                                              spg_cov_solve_stats *stats) {
-    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    const int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_pair_covariances: the fixed vertex is not in the graph");
-    const int D = g->d;
-    const int64_t W = 2 * D, need = (int64_t)n * W * W;
-    std::vector<int32_t> va, vb;
-    std::vector<int64_t> dst;
-    for (int i = 0; i < n; i++) {
-        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
-        const int ia = live_index(g, a), ib = live_index(g, b);
-        const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
-        if (why) {
-            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_pair_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
-            return SPG_EINVAL;
-        }
-        if (!out || cap < need) continue;
-        const int32_t v[2] = {ia, ib};
-        for (int ka = 0; ka < 2; ka++)
-            for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(i * W * W + ka * D * W + kb * D); }
-    }
-    if (!out || cap < need) return need;
-    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_pair_covariances");
-}
-
-extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
-                                                       spg_cov_solve_stats *stats) {
-    if (!g || g->active || n < 0 || (n > 0 && !ids)) return SPG_EINVAL;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    const int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_marginal_covariance: the fixed vertex is not in the graph");
-    const int D = g->d;
-    const int64_t W = (int64_t)n * D, need = W * W;
-    if (W > 46000)
-        return set_err(g->ctx, SPG_ECAPACITY, "spg_graph_joint_marginal_covariance: limited to 46k variables, the bound of spg_graph_covariance");
-    std::vector<int32_t> idx((size_t)n);
-    {
-        std::unordered_set<int32_t> seen;
-        for (int i = 0; i < n; i++) {
-            idx[i] = live_index(g, ids[i]);
-            const char *why = idx[i] < 0 ? "is not in the graph" : !seen.insert(ids[i]).second ? "is listed twice" : nullptr;
-            if (why) {
-                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_marginal_covariance: vertex %d %s", (int)ids[i], why);
-                return SPG_EINVAL;
-            }
-        }
-    }
-    if (!out || cap < need) return need;
-    std::vector<int32_t> va, vb;
-    std::vector<int64_t> dst;
-    va.reserve((size_t)n * n); vb.reserve((size_t)n * n); dst.reserve((size_t)n * n);
-    for (int a = 0; a < n; a++)
-        for (int b = 0; b < n; b++) { va.push_back(idx[a]); vb.push_back(idx[b]); dst.push_back((int64_t)a * D * W + (int64_t)b * D); }
-    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_joint_marginal_covariance");
-}
-
-// ================================================================================= optimize() (8f.1)
-static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<int32_t> &fixed_vertices, spg_optimize_stats *out) {
-    spg_ctx *ctx = g->ctx;
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    std::vector<uint8_t> is_fixed(g->vid.size(), 0);
-    for (int32_t v : fixed_vertices) is_fixed[v] = 1;
-    int64_t n = 0;
-    for (int32_t v : order) if (!is_fixed[v]) n += g->d;
-    // dense up to 12 k unknowns (two n^2 matrices, an n^3 / 3 factorisation per trial), block-sparse beyond
-    const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && n > 12000);
-    if (!sparse && n > 32000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_optimize: dense formulation limited to 32k variables (2 x 8 GB)");
-    if (int rc = sync_device(g)) return rc;
-    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
-    DenseStage st;
-    st.pos.assign(g->vid.size(), -1);
-    int p = 0;
-    for (int32_t v : order) if (!is_fixed[v]) { st.pos[v] = p; p += g->d; }
-    build_dense_stage(g, st);
-    double stats[5] = {0, 0, 0, 0, 0}, secs = 0, info[4] = {0, 0, 0, 0};
-    ctx->err[0] = 0;
-    int rc = (sparse && n > 0)
-                 ? spg::hip_sparse_optimize(spg::hip_backend_stream(&ctx->be), st.in, (int)n, iterations, stats, &secs, info, ctx->err, sizeof ctx->err)
-                 : spg::hip_dense_optimize(spg::hip_backend_stream(&ctx->be), st.in, (int)n, iterations, stats, &secs, ctx->err, sizeof ctx->err);
-    // the estimates changed on the device: refresh the host mirror's copies
-    if (int rc2 = sync_host(g)) return rc2;
-    {
-        // one download of the arena range that holds the free vertices' poses (a copy per vertex costs ~30 us each:
-        // 3 s for a 100 k-pose graph), then only the pose slots are taken over
-        int64_t lo = INT64_MAX, hi = -1;
-        for (int32_t v : order) if (!is_fixed[v]) { lo = std::min(lo, g->vpose[v]); hi = std::max(hi, g->vpose[v] + g->ps); }
-        if (hi > lo) {
-            std::vector<double> tmp((size_t)(hi - lo));
-            if (int rc2 = ctx->be.download(ctx->be.user, tmp.data(), (char *)g->dev + lo * 8, hi - lo)) return rc2;
-            for (int32_t v : order) if (!is_fixed[v]) memcpy(g->host.data() + g->vpose[v], tmp.data() + (g->vpose[v] - lo), (size_t)g->ps * 8);
-        }
-    }
-    if (rc) return rc;
-    if (out) {
-        out->iterations = (int32_t)stats[0]; out->trials = (int32_t)stats[1];
-        out->chi2_initial = stats[2]; out->chi2_final = stats[3]; out->lambda_final = stats[4]; out->device_seconds = secs;
-        out->n = n;
-        out->solver = (sparse && n > 0) ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
-        out->supernodes = (int32_t)info[0]; out->front_bytes = info[2]; out->factor_flops = info[3];
-    }
-    return 0;
-}
-
-extern "C" int spg_sparse_plan(int n, const int32_t *ptr, const int32_t *adj, int pose_dim, const uint8_t *is_marg, int leaf,
-                               spg_sparse_plan_info *info, int32_t *perm, int32_t *sn_first, int32_t *sn_parent, int32_t *sn_level,
-                               int32_t *sn_rowptr, int32_t *rows, int32_t *rel, int64_t rows_cap) {
-    if (n < 0 || !ptr || (pose_dim != 3 && pose_dim != 6) || !info) return SPG_EINVAL;
-    // the row pointers come from the caller: 0-based, non-decreasing, non-negative total — before anything is read through them
-    if (ptr[0] != 0) return SPG_EINVAL;
-    for (int i = 0; i < n; i++) if (ptr[i + 1] < ptr[i]) return SPG_EINVAL;
-    if (!adj && ptr[n] > 0) return SPG_EINVAL;
-    spg::sparse::BlockGraph bg;
-    bg.n = n;
-    bg.ptr.assign(ptr, ptr + n + 1);
-    bg.adj.assign(adj, adj + ptr[n]);
-    for (int32_t u : bg.adj) if (u < 0 || u >= n) return SPG_EINVAL;
-    spg::sparse::Plan P;
-    spg::sparse::build_plan(bg, pose_dim, is_marg, leaf > 0 ? leaf : (pose_dim == 6 ? 32 : 64), P);
-    info->n_supernodes = P.nsn; info->n_marg_supernodes = P.n_marg_sn; info->n_levels = P.nlevels; info->pad_ = 0;
-    info->n_rows = (int64_t)P.rows.size(); info->front_bytes = 8.0 * (double)P.pool; info->flops = P.flops;
-    if (perm) std::copy(P.perm.begin(), P.perm.end(), perm);
-    if (sn_first) std::copy(P.first.begin(), P.first.end(), sn_first);
-    if (sn_parent) std::copy(P.parent.begin(), P.parent.end(), sn_parent);
-    if (sn_level) std::copy(P.level.begin(), P.level.end(), sn_level);
-    if (sn_rowptr) std::copy(P.rowptr.begin(), P.rowptr.end(), sn_rowptr);
-    if (rows_cap >= (int64_t)P.rows.size()) {
-        if (rows) std::copy(P.rows.begin(), P.rows.end(), rows);
-        if (rel) std::copy(P.rel.begin(), P.rel.end(), rel);
-    }
-    return 0;
-}
-
-extern "C" int spg_graph_optimize(spg_graph *g, int iterations, int32_t fixed_id, spg_optimize_stats *out) {
-    if (!g || g->active || iterations < 0) return SPG_EINVAL;
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_optimize needs the HIP backend");
-    std::vector<int32_t> order = live_vertices_by_id(g);
-    int fixed = resolve_fixed(g, order, fixed_id);
-    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize: the fixed vertex is not in the graph");
-    if (order.size() < 2) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize: nothing to optimise");
-    return optimize_with_fixed(g, iterations, std::vector<int32_t>{(int32_t)fixed}, out);
-}
-
-extern "C" int spg_graph_optimize_fixed(spg_graph *g, int iterations, const int32_t *fixed_ids, int n_fixed, spg_optimize_stats *out) {
-    if (!g || g->active || iterations < 0 || n_fixed < 0 || (n_fixed > 0 && !fixed_ids)) return SPG_EINVAL;
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_optimize_fixed needs the HIP backend");
-    std::vector<int32_t> fx;
-    for (int i = 0; i < n_fixed; i++) {
-        auto it = g->vidx.find(fixed_ids[i]);
-        if (it == g->vidx.end() || !g->valive[it->second]) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize_fixed: a fixed vertex is not in the graph");
-        fx.push_back(it->second);
-    }
-    return optimize_with_fixed(g, iterations, fx, out);
-}
-
-extern "C" int spg_graph_chi2(spg_graph *g, double *chi2) {
-    if (!g || !chi2 || g->active) return SPG_EINVAL;
-    // zero iterations with every vertex fixed: the optimiser's entry evaluates chi2 and returns
-    std::vector<int32_t> all;
-    for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) all.push_back((int32_t)i);
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_chi2 needs the HIP backend");
-    spg_optimize_stats st{};
-    int rc = optimize_with_fixed(g, 1, all, &st);
-    if (rc) return rc;
-    *chi2 = st.chi2_initial;
     return 0;
 }

@@ -1,0 +1,491 @@
+// csrc/spg_host_global.cpp — the entry points of include/spg.h that work on a whole graph at once (global KLD,
+// information, covariance and its blocks, optimize / chi2, the symbolic plan): the graph is staged on the host as one
+// DenseGraphIn and handed to the device drivers of spg_dense.hip / spg_sparse.inc. Nothing here touches the scheduler.
+#include "spg_graph_impl.h"
+#include "spg_sparse_plan.hpp"
+
+// ================================================================================= global KLD (a18)
+namespace {
+struct DenseStage {
+    std::vector<int32_t> pos, rowptr, inc, ev;
+    std::vector<spg_edge_ref> er;
+    spg::DenseGraphIn in;
+};
+
+// Live vertex indices in ascending id order.
+std::vector<int32_t> live_vertices_by_id(const spg_graph *g) {
+    std::vector<int32_t> v;
+    for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) v.push_back((int32_t)i);
+    std::sort(v.begin(), v.end(), [&](int32_t a, int32_t b) { return g->vid[a] < g->vid[b]; });
+    return v;
+}
+
+// st.pos must be filled (size = number of vertex slots, -1 = not a variable).
+void build_dense_stage(spg_graph *g, DenseStage &st) {
+    canonicalize_edge_order(g);
+    const int nv = (int)g->vid.size();
+    std::vector<int32_t> remap(g->edges.size(), -1);
+    for (size_t e = 0; e < g->edges.size(); e++) {
+        const GEdge &ge = g->edges[e];
+        if (!ge.alive) continue;
+        remap[e] = (int32_t)st.er.size();
+        st.er.push_back({ge.off, ge.len, ge.kind, (int32_t)st.ev.size(), ge.nv});
+        for (int i = 0; i < ge.nv; i++) st.ev.push_back(edge_verts(g, ge)[i]);
+    }
+    st.rowptr.assign((size_t)nv + 1, 0);
+    for (int v = 0; v < nv; v++) {
+        if (g->valive[v]) {
+            std::vector<int32_t> es;
+            for (int32_t e : g->vr[v].adj) if (remap[e] >= 0) es.push_back(remap[e]);
+            std::sort(es.begin(), es.end());
+            es.erase(std::unique(es.begin(), es.end()), es.end());
+            st.inc.insert(st.inc.end(), es.begin(), es.end());
+        }
+        st.rowptr[v + 1] = (int32_t)st.inc.size();
+    }
+    st.in.D = g->d; st.in.nv = nv; st.in.ne = (int)st.er.size();
+    st.in.pos = st.pos.data(); st.in.vpo = g->vpose.data(); st.in.rowptr = st.rowptr.data(); st.in.inc = st.inc.data();
+    st.in.er = st.er.data(); st.in.ev = st.ev.data(); st.in.n_ev = (int64_t)st.ev.size(); st.in.dev_arena = g->dev;
+}
+
+int resolve_fixed(const spg_graph *g, const std::vector<int32_t> &order, int32_t fixed_id) {
+    if (order.empty()) return -1;
+    if (fixed_id < 0) return order[0];   // the reference skips its first (smallest-id) vertex
+    auto it = g->vidx.find(fixed_id);
+    if (it == g->vidx.end() || !g->valive[it->second]) return -1;
+    return it->second;
+}
+
+// The live vertices outside `fixed` become the variables, in ascending id order: position = scalar offset (step = d)
+// or block number (step = 1).
+void stage_free_vertices(spg_graph *g, const std::vector<int32_t> &order, const std::vector<int32_t> &fixed, int step, DenseStage &st) {
+    std::vector<uint8_t> is_fixed(g->vid.size(), 0);
+    for (int32_t v : fixed) is_fixed[v] = 1;
+    st.pos.assign(g->vid.size(), -1);
+    int p = 0;
+    for (int32_t v : order) if (!is_fixed[v]) { st.pos[v] = p; p += step; }
+    build_dense_stage(g, st);
+}
+
+// Prologue of a call on one graph: the device holds the graph and is idle, the graph is staged, the error text is clear.
+int stage_global(spg_graph *g, const std::vector<int32_t> &order, const std::vector<int32_t> &fixed, int step, DenseStage &st) {
+    if (int rc = sync_device(g)) return rc;
+    if (int rc = g->ctx->be.synchronize(g->ctx->be.user)) return rc;
+    stage_free_vertices(g, order, fixed, step, st);
+    g->ctx->err[0] = 0;
+    return 0;
+}
+
+using DenseMatrixFn = int (*)(void *, const spg::DenseGraphIn &, int, double *, char *, size_t);
+// spg_graph_information / spg_graph_covariance: n x n over every live vertex but the fixed one; limit > 0 bounds n
+int64_t dense_matrix(spg_graph *g, int32_t fixed_id, double *out, int64_t cap, DenseMatrixFn fn, int64_t limit, const char *what) {
+    if (!g || g->active) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    const int64_t n = (int64_t)g->d * ((int64_t)order.size() - 1);
+    if (!out || cap < n * n) return n;
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "%s needs the HIP backend", what);
+    if (limit > 0 && n > limit) return set_err(g->ctx, SPG_ECAPACITY, "%s: dense formulation limited to 46k variables", what);
+    DenseStage st;
+    if (int rc = stage_global(g, order, {fixed}, g->d, st)) return rc;
+    int rc = fn(spg::hip_backend_stream(&g->ctx->be), st.in, (int)n, out, g->ctx->err, sizeof g->ctx->err);
+    return rc ? rc : n;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_information(spg_graph *g, int32_t fixed_id, double *out, int64_t cap) {
+    return dense_matrix(g, fixed_id, out, cap, spg::hip_dense_information, 0, "spg_graph_information");
+}
+
+extern "C" int64_t spg_graph_covariance(spg_graph *g, int32_t fixed_id, double *out, int64_t cap) {
+    return dense_matrix(g, fixed_id, out, cap, spg::hip_dense_covariance, 46000, "spg_graph_covariance");
+}
+
+extern "C" int spg_graph_kullback_leibler(spg_graph *base, spg_graph *other, int32_t fixed_id, spg_kld_terms *out) {
+    if (!base || !other || !out || base->active || other->active) return SPG_EINVAL;
+    spg_ctx *ctx = base->ctx;
+    if (base->d != other->d) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: pose dimensions differ");
+    if (!ctx->is_hip || !other->ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_kullback_leibler needs the HIP backend");
+    if (spg::hip_backend_device(&ctx->be) != spg::hip_backend_device(&other->ctx->be))
+        return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: both graphs must live on the same device");
+    const int d = base->d;
+    std::vector<int32_t> ob = live_vertices_by_id(base), oo = live_vertices_by_id(other);
+    int fb = resolve_fixed(base, ob, fixed_id);
+    if (fb < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the fixed vertex is not in the baseline");
+    const int32_t fid = base->vid[fb];
+    int fo = resolve_fixed(other, oo, fid);
+    if (fo < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the fixed vertex is not in the sparsified graph");
+    // computeIndices (src/graph_wrapper_g2o.cpp:472-499): merge of the two id-sorted vertex lists
+    std::vector<int32_t> kept_b, kept_o, marg_b;
+    {
+        size_t j = 0;
+        for (int32_t v : ob) {
+            if (v == fb) continue;
+            while (j < oo.size() && (oo[j] == fo || other->vid[oo[j]] < base->vid[v])) {
+                if (oo[j] != fo) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the sparsified graph holds a vertex the baseline lacks");
+                j++;
+            }
+            if (j < oo.size() && other->vid[oo[j]] == base->vid[v]) { kept_b.push_back(v); kept_o.push_back(oo[j]); j++; }
+            else marg_b.push_back(v);
+        }
+        for (; j < oo.size(); j++)
+            if (oo[j] != fo) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: the sparsified graph holds a vertex the baseline lacks");
+    }
+    if (kept_b.empty()) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: no common free vertex");
+    const int64_t n_marg = (int64_t)d * marg_b.size(), n_keep = (int64_t)d * kept_b.size();
+    const int64_t Nm = (n_marg + 63) / 64 * 64, Ng = (n_keep + 63) / 64 * 64;
+    const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && Nm + Ng > 46000);
+    if (!sparse && Nm + Ng > 46000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_kullback_leibler: dense formulation limited to 46k variables (16 GB)");
+    if (int rc = sync_device(base)) return rc;
+    if (int rc = sync_device(other)) return rc;
+    if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+    if (other->ctx != ctx) if (int rc = other->ctx->be.synchronize(other->ctx->be.user)) return rc;
+    spg_kld_terms t{};   // the drivers add to the counters and seconds of the struct they are handed
+    t.n_marginalized = n_marg;
+    t.solver = sparse ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
+    DenseStage sb, so;
+    sb.pos.assign(base->vid.size(), -1);
+    so.pos.assign(other->vid.size(), -1);
+    std::vector<int64_t> kvb, kvo;
+    for (size_t i = 0; i < kept_b.size(); i++) { kvb.push_back(base->vpose[kept_b[i]]); kvo.push_back(other->vpose[kept_o[i]]); }
+    void *stream = spg::hip_backend_stream(&ctx->be);
+    int rc;
+    if (sparse) {
+        // block-sparse multifrontal path: positions only number the blocks, the elimination order is the plan's
+        std::vector<uint8_t> is_marg(base->vid.size(), 0);
+        int p = 0;
+        for (int32_t v : ob) if (v != fb) sb.pos[v] = p++;
+        for (int32_t v : marg_b) is_marg[v] = 1;
+        for (size_t i = 0; i < kept_b.size(); i++) so.pos[kept_o[i]] = (int32_t)i;
+        build_dense_stage(base, sb);
+        build_dense_stage(other, so);
+        ctx->err[0] = 0;
+        rc = spg::hip_sparse_kld(stream, sb.in, so.in, is_marg.data(), kept_b.data(), kept_o.data(), (int)kept_b.size(), kvb.data(), kvo.data(), t,
+                                 ctx->err, sizeof ctx->err);
+    } else {
+        int p = 0;
+        for (int32_t v : marg_b) { sb.pos[v] = p; p += d; }
+        for (size_t i = 0; i < kept_b.size(); i++) { sb.pos[kept_b[i]] = (int32_t)(Nm + d * i); so.pos[kept_o[i]] = (int32_t)(d * i); }
+        build_dense_stage(base, sb);
+        build_dense_stage(other, so);
+        ctx->err[0] = 0;
+        rc = spg::hip_dense_kld(stream, sb.in, so.in, (int)n_marg, (int)n_keep, kvb.data(), kvo.data(), t, ctx->err, sizeof ctx->err);
+    }
+    if (rc) return rc;
+    *out = t;
+    return 0;
+}
+
+// ================================================================================= covariance blocks (sparse factor)
+namespace {
+int live_index(const spg_graph *g, int32_t id) {
+    auto it = g->vidx.find(id);
+    return (it == g->vidx.end() || !g->valive[it->second]) ? -1 : it->second;
+}
+bool share_live_edge(const spg_graph *g, int32_t a, int32_t b) {
+    for (int32_t e : g->vr[a].adj) {
+        const GEdge &ge = g->edges[e];
+        if (!ge.alive) continue;
+        const int32_t *vs = edge_verts(g, ge);
+        for (int i = 0; i < ge.nv; i++) if (vs[i] == b) return true;
+    }
+    return false;
+}
+// What cov_blocks and cov_solve share. Each list of vertex indices names the fixed vertex as -1 from here on. Returns 1 when
+// the graph holds nothing but the fixed vertex (every block is zero: out is filled), 0 when the graph is staged
+// (every live vertex but the fixed one is a block, numbered by ascending id), < 0 on an error.
+int cov_stage(spg_graph *g, int fixed, const std::vector<int32_t> &order, std::initializer_list<std::vector<int32_t> *> lists, int64_t need,
+              double *out, const char *what, DenseStage &st) {
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "%s needs the HIP backend", what);
+    for (std::vector<int32_t> *l : lists) for (int32_t &v : *l) if (v == fixed) v = -1;
+    if (need == 0 || order.size() < 2) {
+        std::fill(out, out + need, 0.0);
+        return 1;
+    }
+    return stage_global(g, order, {fixed}, 1, st);
+}
+// K vertex indices per request (-1 = the fixed vertex) -> (K D)^2 doubles per request
+int64_t cov_blocks(spg_graph *g, int fixed, const std::vector<int32_t> &order, int K, std::vector<int32_t> &req, double *out,
+                   spg_cov_stats *stats, const char *what) {
+    const int64_t n = (int64_t)req.size() / K, W = (int64_t)K * g->d, need = n * W * W;
+    DenseStage st;
+    spg_cov_stats cs{};
+    const int staged = cov_stage(g, fixed, order, {&req}, need, out, what, st);
+    if (staged < 0) return staged;
+    if (staged == 0)
+        if (int rc = spg::hip_sparse_cov_blocks(spg::hip_backend_stream(&g->ctx->be), st.in, K, req.data(), (int)n, out, cs, g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (stats) *stats = cs;
+    return need;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_marginal_covariances(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                                  spg_cov_stats *stats) {
+    if (!g || g->active || (ids && n < 0)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_marginal_covariances: the fixed vertex is not in the graph");
+    std::vector<int32_t> req;
+    if (!ids) req = order;
+    else {
+        req.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            req[i] = live_index(g, ids[i]);
+            if (req[i] < 0) {
+                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_marginal_covariances: vertex %d is not in the graph", (int)ids[i]);
+                return SPG_EINVAL;
+            }
+        }
+    }
+    const int64_t need = (int64_t)req.size() * g->d * g->d;
+    if (!out || cap < need) return need;
+    return cov_blocks(g, fixed, order, 1, req, out, stats, "spg_graph_marginal_covariances");
+}
+
+extern "C" int64_t spg_graph_joint_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                               spg_cov_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_covariances: the fixed vertex is not in the graph");
+    std::vector<int32_t> req((size_t)2 * n);
+    for (int i = 0; i < n; i++) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        const int va = live_index(g, a), vb = live_index(g, b);
+        const char *why = (va < 0 || vb < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same"
+                          : !share_live_edge(g, va, vb) ? "the vertices share no live edge" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
+            return SPG_EINVAL;
+        }
+        req[2 * i] = va;
+        req[2 * i + 1] = vb;
+    }
+    const int64_t W = 2 * g->d, need = (int64_t)n * W * W;
+    if (!out || cap < need) return need;
+    return cov_blocks(g, fixed, order, 2, req, out, stats, "spg_graph_joint_covariances");
+}
+
+extern "C" int spg_graph_marginal_kld(spg_graph *base, spg_graph *other, int32_t fixed_id, int32_t *ids, double *kld, int cap,
+                                      spg_cov_stats *stats) {
+    if (!base || !other || base->active || other->active) return SPG_EINVAL;
+    spg_ctx *ctx = base->ctx;
+    if (base->d != other->d) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: pose dimensions differ");
+    std::vector<int32_t> ob = live_vertices_by_id(base), oo = live_vertices_by_id(other);
+    const int fb = resolve_fixed(base, ob, fixed_id);
+    if (fb < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the baseline");
+    const int fo = resolve_fixed(other, oo, base->vid[fb]);
+    if (fo < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: the fixed vertex is not in the sparsified graph");
+    std::vector<int32_t> vb, vo, out_ids;
+    for (int32_t v : oo) {
+        if (v == fo) continue;
+        const int u = live_index(base, other->vid[v]);
+        if (u < 0) {
+            snprintf(ctx->err, sizeof ctx->err, "spg_graph_marginal_kld: the sparsified graph holds vertex %d, which the baseline lacks", (int)other->vid[v]);
+            return SPG_EINVAL;
+        }
+        vb.push_back(u);
+        vo.push_back(v);
+        out_ids.push_back(other->vid[v]);
+    }
+    const int nk = (int)vo.size();
+    if (!ids || !kld || cap < nk) return nk;
+    if (!ctx->is_hip || !other->ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_marginal_kld needs the HIP backend");
+    if (spg::hip_backend_device(&ctx->be) != spg::hip_backend_device(&other->ctx->be))
+        return set_err(ctx, SPG_EINVAL, "spg_graph_marginal_kld: both graphs must live on the same device");
+    spg_cov_stats cs{};
+    if (nk > 0) {
+        if (int rc = sync_device(base)) return rc;
+        if (int rc = sync_device(other)) return rc;
+        if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+        if (other->ctx != ctx) if (int rc = other->ctx->be.synchronize(other->ctx->be.user)) return rc;
+        DenseStage sb, so;
+        stage_free_vertices(base, ob, {fb}, 1, sb);
+        stage_free_vertices(other, oo, {fo}, 1, so);
+        std::vector<int64_t> kvb, kvo;
+        for (int i = 0; i < nk; i++) { kvb.push_back(base->vpose[vb[i]]); kvo.push_back(other->vpose[vo[i]]); }
+        ctx->err[0] = 0;
+        int rc = spg::hip_sparse_marginal_kld(spg::hip_backend_stream(&ctx->be), sb.in, so.in, vb.data(), vo.data(), nk, kvb.data(), kvo.data(),
+                                              kld, cs, ctx->err, sizeof ctx->err);
+        if (rc) return rc;
+    }
+    std::copy(out_ids.begin(), out_ids.end(), ids);
+    if (stats) *stats = cs;
+    return nk;
+}
+
+// ================================================================================= covariance of arbitrary pairs / sets
+namespace {
+// D x D sub-blocks Sigma(va[i], vb[i]) (vertex indices) at out + dst[i], row stride ld
+int64_t cov_solve(spg_graph *g, int fixed, const std::vector<int32_t> &order, std::vector<int32_t> &va, std::vector<int32_t> &vb,
+                  const std::vector<int64_t> &dst, int32_t ld, int64_t need, double *out, spg_cov_solve_stats *stats, const char *what) {
+    DenseStage st;
+    spg_cov_solve_stats cs{};
+    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, out, what, st);
+    if (staged < 0) return staged;
+    if (staged == 0)
+        if (int rc = spg::hip_sparse_cov_solve(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), ld, (int64_t)va.size(), need, out,
+                                               cs, g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (stats) *stats = cs;
+    return need;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_pair_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *out, int64_t cap,
+                                              spg_cov_solve_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !pairs)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_pair_covariances: the fixed vertex is not in the graph");
+    const int D = g->d;
+    const int64_t W = 2 * D, need = (int64_t)n * W * W;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    for (int i = 0; i < n; i++) {
+        const int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
+        const int ia = live_index(g, a), ib = live_index(g, b);
+        const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_pair_covariances: pair %d (%d, %d): %s", i, (int)a, (int)b, why);
+            return SPG_EINVAL;
+        }
+        if (!out || cap < need) continue;
+        const int32_t v[2] = {ia, ib};
+        for (int ka = 0; ka < 2; ka++)
+            for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(i * W * W + ka * D * W + kb * D); }
+    }
+    if (!out || cap < need) return need;
+    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_pair_covariances");
+}
+
+extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
+                                                       spg_cov_solve_stats *stats) {
+    if (!g || g->active || n < 0 || (n > 0 && !ids)) return SPG_EINVAL;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_joint_marginal_covariance: the fixed vertex is not in the graph");
+    const int D = g->d;
+    const int64_t W = (int64_t)n * D, need = W * W;
+    if (W > 46000)
+        return set_err(g->ctx, SPG_ECAPACITY, "spg_graph_joint_marginal_covariance: limited to 46k variables, the bound of spg_graph_covariance");
+    std::vector<int32_t> idx((size_t)n);
+    {
+        std::unordered_set<int32_t> seen;
+        for (int i = 0; i < n; i++) {
+            idx[i] = live_index(g, ids[i]);
+            const char *why = idx[i] < 0 ? "is not in the graph" : !seen.insert(ids[i]).second ? "is listed twice" : nullptr;
+            if (why) {
+                snprintf(g->ctx->err, sizeof g->ctx->err, "spg_graph_joint_marginal_covariance: vertex %d %s", (int)ids[i], why);
+                return SPG_EINVAL;
+            }
+        }
+    }
+    if (!out || cap < need) return need;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    va.reserve((size_t)n * n); vb.reserve((size_t)n * n); dst.reserve((size_t)n * n);
+    for (int a = 0; a < n; a++)
+        for (int b = 0; b < n; b++) { va.push_back(idx[a]); vb.push_back(idx[b]); dst.push_back((int64_t)a * D * W + (int64_t)b * D); }
+    return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_joint_marginal_covariance");
+}
+
+// ================================================================================= optimize() (8f.1)
+static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<int32_t> &fixed_vertices, spg_optimize_stats *out) {
+    spg_ctx *ctx = g->ctx;
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    std::vector<uint8_t> is_fixed(g->vid.size(), 0);
+    for (int32_t v : fixed_vertices) is_fixed[v] = 1;
+    int64_t n = 0;
+    for (int32_t v : order) if (!is_fixed[v]) n += g->d;
+    // dense up to 12 k unknowns (two n^2 matrices, an n^3 / 3 factorisation per trial), block-sparse beyond
+    const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && n > 12000);
+    if (!sparse && n > 32000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_optimize: dense formulation limited to 32k variables (2 x 8 GB)");
+    DenseStage st;
+    if (int rc = stage_global(g, order, fixed_vertices, g->d, st)) return rc;
+    spg_optimize_stats os{};
+    os.n = n;
+    os.solver = (sparse && n > 0) ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
+    auto *run = os.solver == SPG_SOLVER_SPARSE ? spg::hip_sparse_optimize : spg::hip_dense_optimize;
+    int rc = run(spg::hip_backend_stream(&ctx->be), st.in, (int)n, iterations, os, ctx->err, sizeof ctx->err);
+    // the estimates changed on the device: refresh the host mirror's copies
+    if (int rc2 = sync_host(g)) return rc2;
+    {
+        // one download of the arena range that holds the free vertices' poses (a copy per vertex costs ~30 us each:
+        // 3 s for a 100 k-pose graph), then only the pose slots are taken over
+        int64_t lo = INT64_MAX, hi = -1;
+        for (int32_t v : order) if (!is_fixed[v]) { lo = std::min(lo, g->vpose[v]); hi = std::max(hi, g->vpose[v] + g->ps); }
+        if (hi > lo) {
+            std::vector<double> tmp((size_t)(hi - lo));
+            if (int rc2 = ctx->be.download(ctx->be.user, tmp.data(), (char *)g->dev + lo * 8, hi - lo)) return rc2;
+            for (int32_t v : order) if (!is_fixed[v]) memcpy(g->host.data() + g->vpose[v], tmp.data() + (g->vpose[v] - lo), (size_t)g->ps * 8);
+        }
+    }
+    if (rc) return rc;
+    if (out) *out = os;
+    return 0;
+}
+
+extern "C" int spg_sparse_plan(int n, const int32_t *ptr, const int32_t *adj, int pose_dim, const uint8_t *is_marg, int leaf,
+                               spg_sparse_plan_info *info, int32_t *perm, int32_t *sn_first, int32_t *sn_parent, int32_t *sn_level,
+                               int32_t *sn_rowptr, int32_t *rows, int32_t *rel, int64_t rows_cap) {
+    if (n < 0 || !ptr || (pose_dim != 3 && pose_dim != 6) || !info) return SPG_EINVAL;
+    // the row pointers come from the caller: 0-based, non-decreasing, non-negative total — before anything is read through them
+    if (ptr[0] != 0) return SPG_EINVAL;
+    for (int i = 0; i < n; i++) if (ptr[i + 1] < ptr[i]) return SPG_EINVAL;
+    if (!adj && ptr[n] > 0) return SPG_EINVAL;
+    spg::sparse::BlockGraph bg;
+    bg.n = n;
+    bg.ptr.assign(ptr, ptr + n + 1);
+    bg.adj.assign(adj, adj + ptr[n]);
+    for (int32_t u : bg.adj) if (u < 0 || u >= n) return SPG_EINVAL;
+    spg::sparse::Plan P;
+    spg::sparse::build_plan(bg, pose_dim, is_marg, leaf > 0 ? leaf : (pose_dim == 6 ? 32 : 64), P);
+    info->n_supernodes = P.nsn; info->n_marg_supernodes = P.n_marg_sn; info->n_levels = P.nlevels; info->pad_ = 0;
+    info->n_rows = (int64_t)P.rows.size(); info->front_bytes = 8.0 * (double)P.pool; info->flops = P.flops;
+    if (perm) std::copy(P.perm.begin(), P.perm.end(), perm);
+    if (sn_first) std::copy(P.first.begin(), P.first.end(), sn_first);
+    if (sn_parent) std::copy(P.parent.begin(), P.parent.end(), sn_parent);
+    if (sn_level) std::copy(P.level.begin(), P.level.end(), sn_level);
+    if (sn_rowptr) std::copy(P.rowptr.begin(), P.rowptr.end(), sn_rowptr);
+    if (rows_cap >= (int64_t)P.rows.size()) {
+        if (rows) std::copy(P.rows.begin(), P.rows.end(), rows);
+        if (rel) std::copy(P.rel.begin(), P.rel.end(), rel);
+    }
+    return 0;
+}
+
+extern "C" int spg_graph_optimize(spg_graph *g, int iterations, int32_t fixed_id, spg_optimize_stats *out) {
+    if (!g || g->active || iterations < 0) return SPG_EINVAL;
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_optimize needs the HIP backend");
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize: the fixed vertex is not in the graph");
+    if (order.size() < 2) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize: nothing to optimise");
+    return optimize_with_fixed(g, iterations, std::vector<int32_t>{(int32_t)fixed}, out);
+}
+
+extern "C" int spg_graph_optimize_fixed(spg_graph *g, int iterations, const int32_t *fixed_ids, int n_fixed, spg_optimize_stats *out) {
+    if (!g || g->active || iterations < 0 || n_fixed < 0 || (n_fixed > 0 && !fixed_ids)) return SPG_EINVAL;
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_optimize_fixed needs the HIP backend");
+    std::vector<int32_t> fx;
+    for (int i = 0; i < n_fixed; i++) {
+        auto it = g->vidx.find(fixed_ids[i]);
+        if (it == g->vidx.end() || !g->valive[it->second]) return set_err(g->ctx, SPG_EINVAL, "spg_graph_optimize_fixed: a fixed vertex is not in the graph");
+        fx.push_back(it->second);
+    }
+    return optimize_with_fixed(g, iterations, fx, out);
+}
+
+extern "C" int spg_graph_chi2(spg_graph *g, double *chi2) {
+    if (!g || !chi2 || g->active) return SPG_EINVAL;
+    // zero iterations with every vertex fixed: the optimiser's entry evaluates chi2 and returns
+    std::vector<int32_t> all;
+    for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) all.push_back((int32_t)i);
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_chi2 needs the HIP backend");
+    spg_optimize_stats st{};
+    int rc = optimize_with_fixed(g, 1, all, &st);
+    if (rc) return rc;
+    *chi2 = st.chi2_initial;
+    return 0;
+}

@@ -64,11 +64,14 @@ struct DenseGraphIn {
     int64_t n_ev = 0;
     const void *dev_arena = nullptr;    // device arena of the graph
 };
+// Results of the global-path drivers below land in the public structs of include/spg.h. One rule for all of them: a
+// driver ADDS to the counters and seconds of the struct it is handed (the marginal KLD runs two factorisations into one)
+// and assigns the values that are results (terms, chi2, iterations); the caller zero-initialises the struct and sets the
+// fields the device side does not know (n_marginalized, optimize's n, solver). Errors: code returned, text in err.
 int hip_dense_information(void *stream, const DenseGraphIn &in, int n, double *out, char *err, size_t errlen);
 int hip_dense_covariance(void *stream, const DenseGraphIn &in, int n, double *out, char *err, size_t errlen);
 int hip_dense_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, int n_marg, int n_keep,
-                  const int64_t *kept_vpo_base, const int64_t *kept_vpo_other, double *terms, double *seconds,
-                  char *err, size_t errlen);
+                  const int64_t *kept_vpo_base, const int64_t *kept_vpo_other, spg_kld_terms &out, char *err, size_t errlen);
 
 // One GLC Dense blanket too large for the LDS kernel, dense in HBM on the fp64 matrix cores (spg_dense.hip)
 int hip_big_glc_dense(void *stream, const DenseGraphIn &local_graph, int m, int k, int Nm, int64_t new_off, double *orec, int n_new_max, int tag,
@@ -77,32 +80,26 @@ int hip_big_glc_dense(void *stream, const DenseGraphIn &local_graph, int m, int 
 int hip_la_test(int op, int M, int N, int K, int flags, int mode, double *A, int ra, int lda, double *B, int rb, int ldb, double *C, int rc, int ldc, int *ok);
 // frees the scratch the large-blanket pipeline keeps between calls (device block + pinned staging); called when a backend goes
 void hip_big_release_scratch();
-int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, double *stats, double *seconds,
-                       char *err, size_t errlen);
+int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen);
 
 // Block-sparse multifrontal path of the same two calls (spg_sparse.inc, symbolic phase in spg_sparse_plan.hpp).
-// info[4]: supernodes, levels of the assembly tree, bytes of fronts, flops of one factorisation.
-int hip_sparse_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, double *stats, double *seconds, double *info,
-                        char *err, size_t errlen);
+int hip_sparse_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen);
 int hip_sparse_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const uint8_t *is_marg_vertex,
                    const int32_t *kept_b, const int32_t *kept_o, int nk, const int64_t *kept_vpo_base, const int64_t *kept_vpo_other,
-                   double *terms, double *seconds, double *info, char *err, size_t errlen);
+                   spg_kld_terms &out, char *err, size_t errlen);
 // Covariance blocks from the selected inverse over the graph's own plan (spg_sparse.inc). in.pos >= 0: the free
 // vertices. req: n requests of K (1 or 2) vertex indices, -1 = the fixed vertex; out (host): n (K D)^2 doubles, row-major.
-// info[4] += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops; *seconds += device time.
-int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, double *seconds, double *info,
+int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, spg_cov_stats &stats,
                           char *err, size_t errlen);
 // Covariance sub-blocks of arbitrary vertex pairs (spg_sparse.inc): sub-block i = Sigma(va[i], vb[i]) (D x D; -1 = the
 // fixed vertex, zero) lands at out[dst[i]] with row stride ld (host, out_len doubles). Diagonal and in-pattern blocks
-// come from the selected inverse, the others from multi-RHS column solves through the fronts. info[8] += supernodes,
-// bytes of fronts and Z blocks, factorisation flops, selected-inverse flops, columns solved, RHS batches, solve flops,
-// solve seconds; *seconds += device time of everything.
+// come from the selected inverse, the others from multi-RHS column solves through the fronts.
 int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
-                         int64_t out_len, double *out, double *seconds, double *info, char *err, size_t errlen);
+                         int64_t out_len, double *out, spg_cov_solve_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,
-                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, double *seconds, double *info, char *err, size_t errlen);
+                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, spg_cov_stats &stats, char *err, size_t errlen);
 
 // Interior-point NFR (spg_nfr_ip.hip): blankets of the Dense / Subgraph patterns without a closed form, one workgroup
 // each, everything in a per-blanket slice of a global workspace.

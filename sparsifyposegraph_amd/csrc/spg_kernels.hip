@@ -2333,8 +2333,8 @@ static int hip_run_round(void *user, void *arena, const spg_round_desc *rd) {
                 in.D = D; in.nv = bd.n_vert; in.ne = bd.n_edge;
                 in.pos = pos.data(); in.vpo = lvpo.data(); in.rowptr = rowptr.data(); in.inc = inc.data();
                 in.er = rd->edges + bd.edge_begin; in.ev = rd->edge_vert; in.n_ev = rd->n_edge_vert_total; in.dev_arena = arena;
-                double lm_stats[8] = {0}, lm_secs = 0;
-                if (int lrc = spg::hip_dense_optimize((void *)S.stream, in, D * (bd.n_vert - 1), 10, lm_stats, &lm_secs, hb->err, sizeof hb->err)) return lrc;
+                spg_optimize_stats lm_stats{};
+                if (int lrc = spg::hip_dense_optimize((void *)S.stream, in, D * (bd.n_vert - 1), 10, lm_stats, hb->err, sizeof hb->err)) return lrc;
             }
             ia.vpo = (const int64_t *)d_vpo2;
             ia.lin_point = SPG_LIN_GLOBAL;   // the scratch poses ARE the local linearisation point: taken as they are

@@ -797,12 +797,10 @@ struct SparseSolver {
                 hipLaunchKernelGGL(sp_diag_items_kernel, dim3(st.count), dim3(64), 0, s, (const DiagItem *)diag_items.p + st.begin, bad);
                 break;
             case SpStep::EXTADD:
-                if (D == 6) hipLaunchKernelGGL((sp_extend_add_kernel<6>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin);
-                else hipLaunchKernelGGL((sp_extend_add_kernel<3>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin);
+                by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_extend_add_kernel<decltype(d)::value>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin); });
                 break;
             case SpStep::GATHER:
-                if (D == 6) hipLaunchKernelGGL((sp_gather_sigma_kernel<6>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin);
-                else hipLaunchKernelGGL((sp_gather_sigma_kernel<3>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin);
+                by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_gather_sigma_kernel<decltype(d)::value>), dim3(st.count, st.ymax), dim3(256), 0, s, (const EaPair *)pairs.p + st.begin); });
                 break;
             }
         }
@@ -812,8 +810,7 @@ struct SparseSolver {
     int assemble(hipStream_t s, const GraphBufs &gb, double *b, int *bad) {
         if (hipMemsetAsync(pool.p, 0, (size_t)std::max<int64_t>(plan.pool, 1) * 8, s) != hipSuccess) return SPG_EHIP;
         FrontSink sink{dev, bad ? bad : (int *)own_bad.p};
-        if (D == 6) launch_assemble_into<6>(gb, sink, s, b);
-        else launch_assemble_into<3>(gb, sink, s, b);
+        by_dim(D, [&](auto d) { launch_assemble_into<decltype(d)::value>(gb, sink, s, b); });
         return 0;
     }
     // fronts <- the partial factorisations of the staged graph's H (no shift): the step the global KLD and the
@@ -881,6 +878,11 @@ struct SparseSolver {
         for (int l = 0; l < P.nlevels; l++)
             hipLaunchKernelGGL(sp_backward_kernel, dim3(P.level_ptr[l + 1] - P.level_ptr[l]), dim3(level_threads(l)), 0, s, dev, P.level_ptr[l], x, 1, (double *)partial.p);
         hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)partial.p, P.nsn, out, slot);
+    }
+    // stats += what this solver (initialised with_selinv) costs: supernodes, bytes of fronts and Z blocks, flops
+    void count_into(spg_cov_stats &st) const {
+        st.supernodes += plan.nsn; st.front_bytes += (double)(plan.pool + zpool_len) * 8;
+        st.factor_flops += plan.flops; st.selinv_flops += selinv_flops;
     }
     int selected_inverse(hipStream_t s, int *bad) {
         if (hipMemsetAsync(zpool.p, 0, (size_t)std::max<int64_t>(zpool_len, 1) * 8, s) != hipSuccess) return SPG_EHIP;
@@ -957,6 +959,13 @@ bool cov_force_solve() {
     return v;
 }
 
+// the device flags of the covariance drivers: [0] a pivot failed, [1] a request fell outside the fronts
+int cov_bad_flags(const int *h_bad, char *err, size_t errlen) {
+    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); return SPG_ENOTPD; }
+    if (h_bad[1]) { snprintf(err, errlen, "covariance blocks: a requested pair lies outside the fronts of the factorisation"); return SPG_ESTATE; }
+    return 0;
+}
+
 // block (qa, qb) of positions lies inside the fronts, where FrontSink::locate finds Sigma after the selected inverse
 bool in_fronts(const Plan &P, int qa, int qb) {
     const int qu = std::min(qa, qb), qv = std::max(qa, qb), s = P.sn_of[qu];
@@ -999,6 +1008,16 @@ void choose_columns(int nblocks, const std::vector<int32_t> &x, const std::vecto
         take(v);
     }
 }
+
+// HIPCHK in the wording of the column solves' messages
+#define COLCHK(what, x)                                                                                                  \
+    do {                                                                                                                 \
+        hipError_t e_ = (x);                                                                                             \
+        if (e_ != hipSuccess) {                                                                                          \
+            snprintf(err, errlen, "covariance column solves: %s failed: %s", what, hipGetErrorString(e_));             \
+            return SPG_EHIP;                                                                                             \
+        }                                                                                                                \
+    } while (0)
 
 struct ColumnSolves {
     enum Kind { GEMM, EXTADD, GATHER, SEED, CROSS };
@@ -1197,24 +1216,18 @@ struct ColumnSolves {
     }
     // every batch: panels zeroed, seeded, forward, backward, requested rows -> cross (n requests x D^2)
     int run(hipStream_t s, double *cross, char *err, size_t errlen) {
-        int rc = 0;
         int64_t ws_len = 0;
         if (cols.empty()) return 0;
-        if ((rc = plan_batches(ws_len, err, errlen))) return rc;
+        if (int rc = plan_batches(ws_len, err, errlen)) return rc;
         DevBuf ws, blob;
         size_t blob_cap = 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
         std::vector<char> hb;
-        auto fail = [&](const char *what, hipError_t e) {
-            snprintf(err, errlen, "covariance column solves: %s failed: %s", what, hipGetErrorString(e));
-            return SPG_EHIP;
-        };
-        hipError_t e;
-        if ((e = hipMalloc(&ws.p, (size_t)std::max<int64_t>(ws_len, 1) * 8)) != hipSuccess) {
+        if (hipMalloc(&ws.p, (size_t)std::max<int64_t>(ws_len, 1) * 8) != hipSuccess) {
             snprintf(err, errlen, "covariance column solves: hipMalloc of %.2f GB of panels failed", ws_len * 8e-9);
             return SPG_ECAPACITY;
         }
-        if ((e = hipEventCreate(&e0)) != hipSuccess || (e = hipEventCreate(&e1)) != hipSuccess) { rc = fail("hipEventCreate", e); goto out; }
+        EventTimer timer;   // one batch at a time
+        float ms = 0;
         for (int b = 0; b < nbatch; b++) {
             build(b, (double *)ws.p);
             // one upload per batch: gemm items | panel pairs | seeds | cross sources | cross destinations
@@ -1227,35 +1240,33 @@ struct ColumnSolves {
             memcpy(hb.data() + o_cs, csrc.data(), o_cd - o_cs);
             memcpy(hb.data() + o_cd, cdst.data(), nbytes - o_cd);
             if (b > 0) {   // the previous batch still reads the blob and the panels
-                float ms = 0;
-                if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = fail("a batch", e); goto out; }
-                if ((e = hipEventElapsedTime(&ms, e0, e1)) != hipSuccess) { rc = fail("hipEventElapsedTime", e); goto out; }
+                COLCHK("a batch", hipStreamSynchronize(s));
+                COLCHK("hipEventElapsedTime", timer.ms(ms));
                 seconds += 1e-3 * ms;
             }
             if (nbytes > blob_cap) {
                 if (blob.p) { (void)hipFree(blob.p); blob.p = nullptr; }
                 blob_cap = nbytes + nbytes / 4;
-                if ((e = hipMalloc(&blob.p, blob_cap)) != hipSuccess) { rc = fail("hipMalloc of the item lists", e); goto out; }
+                COLCHK("hipMalloc of the item lists", hipMalloc(&blob.p, blob_cap));
             }
-            if ((e = hipMemcpy(blob.p, hb.data(), nbytes, hipMemcpyHostToDevice)) != hipSuccess) { rc = fail("uploading the item lists", e); goto out; }
+            COLCHK("uploading the item lists", hipMemcpy(blob.p, hb.data(), nbytes, hipMemcpyHostToDevice));
             const char *B = (const char *)blob.p;
             const int R = width(b);
             int64_t len = 0;
             for (int sn : P.level_sn) if (fw[sn] == stamp || bw[sn] == stamp) len += (int64_t)P.ld(sn) * R;
-            if ((e = hipEventRecord(e0, s)) != hipSuccess) { rc = fail("hipEventRecord", e); goto out; }
-            if ((e = hipMemsetAsync(ws.p, 0, (size_t)std::max<int64_t>(len, 1) * 8, s)) != hipSuccess) { rc = fail("hipMemsetAsync", e); goto out; }
+            COLCHK(timer.made != hipSuccess ? "hipEventCreate" : "hipEventRecord", timer.start(s));
+            COLCHK("hipMemsetAsync", hipMemsetAsync(ws.p, 0, (size_t)std::max<int64_t>(len, 1) * 8, s));
             for (const Step &st : steps) {
+                const PanelPair *pairs = (const PanelPair *)(B + o_pp) + st.begin;
                 switch (st.kind) {
                 case GEMM:
                     hipLaunchKernelGGL(sp_gemm_items_kernel, dim3(st.count), dim3(256), 0, s, (const GemmItem *)B + st.begin);
                     break;
                 case EXTADD:
-                    if (D == 6) hipLaunchKernelGGL((sp_panel_rows_kernel<6, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
-                    else hipLaunchKernelGGL((sp_panel_rows_kernel<3, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
                     break;
                 case GATHER:
-                    if (D == 6) hipLaunchKernelGGL((sp_panel_rows_kernel<6, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
-                    else hipLaunchKernelGGL((sp_panel_rows_kernel<3, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, (const PanelPair *)(B + o_pp) + st.begin);
+                    by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
                     break;
                 case SEED:
                     hipLaunchKernelGGL(sp_panel_seed_kernel, dim3((st.count + 255) / 256), dim3(256), 0, s, (double *)ws.p, (const int64_t *)(B + o_sd), st.count);
@@ -1267,19 +1278,13 @@ struct ColumnSolves {
                     break;
                 }
             }
-            if ((e = hipGetLastError()) != hipSuccess) { rc = fail("a launch", e); goto out; }
-            if ((e = hipEventRecord(e1, s)) != hipSuccess) { rc = fail("hipEventRecord", e); goto out; }
+            COLCHK("a launch", hipGetLastError());
+            COLCHK("hipEventRecord", timer.stop(s));
         }
-        {
-            float ms = 0;
-            if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = fail("a batch", e); goto out; }
-            if ((e = hipEventElapsedTime(&ms, e0, e1)) != hipSuccess) { rc = fail("hipEventElapsedTime", e); goto out; }
-            seconds += 1e-3 * ms;
-        }
-    out:
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        return rc;
+        COLCHK("a batch", hipStreamSynchronize(s));
+        COLCHK("hipEventElapsedTime", timer.ms(ms));
+        seconds += 1e-3 * ms;
+        return 0;
     }
 };
 
@@ -1326,8 +1331,7 @@ int sparse_plan_debug(int n, const int32_t *ptr, const int32_t *adj, int D, cons
 
 // optimize() with the sparse solver. in.pos: >= 0 for every free vertex (any distinct values; their order numbers the
 // blocks), -1 otherwise. On return the arena holds the optimised estimates.
-int hip_sparse_optimize(void *stream, const DenseGraphIn &in_, int n, int iterations, double *stats, double *seconds, double *info,
-                        char *err, size_t errlen) {
+int hip_sparse_optimize(void *stream, const DenseGraphIn &in_, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     const int D = in_.D, nb = n / D;
     // blocks by ascending pos
@@ -1347,13 +1351,13 @@ int hip_sparse_optimize(void *stream, const DenseGraphIn &in_, int n, int iterat
     DenseGraphIn in = in_;
     in.pos = pos_new.data();
     auto lin = std::make_unique<SparseLM>();
-    if (info) { info[0] = plan.nsn; info[1] = plan.nlevels; info[2] = (double)plan.pool * 8; info[3] = plan.flops; }
+    out.supernodes += plan.nsn; out.front_bytes += (double)plan.pool * 8; out.factor_flops += plan.flops;
     int rc = lin->sp.init(std::move(plan), false, err, errlen);
     if (rc) return rc;
     lin->nvec = std::max(n, 1);
     GraphBufs gb;
     if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for the optimiser failed (%d)", rc); return rc; }
-    return lm_run(s, in, gb, n, lin->nvec, iterations, *lin, stats, seconds, err, errlen);
+    return lm_run(s, in, gb, n, lin->nvec, iterations, *lin, out, err, errlen);
 }
 
 // Global KLD with the sparse solver. base.pos: >= 0 for the baseline's free vertices (ascending = the caller's order),
@@ -1361,7 +1365,7 @@ int hip_sparse_optimize(void *stream, const DenseGraphIn &in_, int n, int iterat
 // kept_*: the common vertices as indices into the two graphs (same order), with their pose offsets.
 int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &other_, const uint8_t *is_marg_vertex,
                    const int32_t *kept_b, const int32_t *kept_o, int nk, const int64_t *kept_vpo_base, const int64_t *kept_vpo_other,
-                   double *terms, double *seconds, double *info, char *err, size_t errlen) {
+                   spg_kld_terms &terms, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     int rc = 0;
     const int D = base_.D;
@@ -1371,7 +1375,7 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &
     plan_of(base_, is_marg_vertex, pb, pos_b);
     plan_of(other_, nullptr, po, pos_o);
     for (int i = 0; i < nk; i++) pos_ob[kept_o[i]] = pos_b[kept_b[i]];    // other's vertices at the baseline's positions
-    if (info) { info[0] = pb.nsn; info[1] = pb.nlevels; info[2] = (double)(pb.pool + po.pool) * 8; info[3] = pb.flops + po.flops; }
+    terms.supernodes += pb.nsn; terms.front_bytes += (double)(pb.pool + po.pool) * 8; terms.factor_flops += pb.flops + po.flops;
     const int n_marg_sn = pb.n_marg_sn;
     auto sb = std::make_unique<SparseSolver>(), so = std::make_unique<SparseSolver>();
     if ((rc = sb->init(std::move(pb), true, err, errlen)) || (rc = so->init(std::move(po), false, err, errlen))) return rc;
@@ -1381,80 +1385,66 @@ int hip_sparse_kld(void *stream, const DenseGraphIn &base_, const DenseGraphIn &
     other_at_base.pos = pos_ob.data();
     GraphBufs gbb, gbo, gbx;
     DevBuf bad, outb, diff, tpart, vb, vo, dpos;
-    int h_bad[2] = {0, 0};
-    double h_out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
     std::vector<int32_t> kpos((size_t)nk);
     for (int i = 0; i < nk; i++) kpos[i] = pos_o[kept_o[i]];
     HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
     HIPCHK(hipMalloc(&outb.p, 8 * 8));
     HIPCHK(hipMalloc(&diff.p, (size_t)std::max(nk, 1) * D * 8 * 2));
     HIPCHK(hipMalloc(&tpart.p, (size_t)std::max(other_.nv, 1) * 8));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    EventTimer timer;
     if ((rc = upload(vb, kept_vpo_base, (size_t)nk, s)) || (rc = upload(vo, kept_vpo_other, (size_t)nk, s)) || (rc = upload(dpos, kpos.data(), (size_t)nk, s)) ||
         (rc = stage_graph(base, gbb, s)) || (rc = stage_graph(other, gbo, s)) || (rc = stage_graph(other_at_base, gbx, s))) {
         snprintf(err, errlen, "staging the graphs for the sparse KLD failed (%d)", rc);
-        goto done;
+        return rc;
     }
-    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(timer.start(s));
     HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
     HIPCHK(hipMemsetAsync(tpart.p, 0, (size_t)std::max(other_.nv, 1) * 8, s));
-    {
-        int *bad0 = (int *)bad.p, *bad1 = (int *)bad.p + 1;
-        double *out = (double *)outb.p, *dk = (double *)diff.p, *dperm = (double *)diff.p + (size_t)std::max(nk, 1) * D;
-        // sparsified graph: factor, log det, Mahalanobis term || L_x^T diff ||^2
-        if ((rc = so->factorise(s, gbo, bad1))) goto done;
-        so->logdiag(s, 0, out, 1);
-        if (D == 6) hipLaunchKernelGGL((pose_diff_kernel<6>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, dk);
-        else hipLaunchKernelGGL((pose_diff_kernel<3>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)base.dev_arena, (const int64_t *)vb.p, (const double *)other.dev_arena, (const int64_t *)vo.p, nk, dk);
-        hipLaunchKernelGGL(scatter_blocks_kernel, dim3((nk * D + 255) / 256), dim3(256), 0, s, (const double *)dk, (const int32_t *)dpos.p, nk, D, dperm);
-        so->ltx_norm2(s, dperm, out, 3);
-        // baseline: marginalised blocks first; log det of the marginal from the kept supernodes; selected inverse
-        if ((rc = sb->factorise(s, gbb, bad0))) goto done;
-        sb->logdiag(s, n_marg_sn, out, 2);
-        if ((rc = sb->selected_inverse(s, bad0))) goto done;
-        // trace(Sigma_kept Lambda_x): the sparsified graph's Hessian blocks against the selected inverse
-        {
-            TraceSink ts{FrontSink{sb->dev, bad0}, (double *)tpart.p, 0.0};
-            if (D == 6) launch_assemble_into<6>(gbx, ts, s, nullptr);
-            else launch_assemble_into<3>(gbx, ts, s, nullptr);
-            hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)tpart.p, other_.nv, out, 0);
-        }
-    }
+    int *bad0 = (int *)bad.p, *bad1 = (int *)bad.p + 1;
+    double *out = (double *)outb.p, *dk = (double *)diff.p, *dperm = (double *)diff.p + (size_t)std::max(nk, 1) * D;
+    // sparsified graph: factor, log det, Mahalanobis term || L_x^T diff ||^2
+    if ((rc = so->factorise(s, gbo, bad1))) return rc;
+    so->logdiag(s, 0, out, 1);
+    launch_pose_diff(D, s, base.dev_arena, (const int64_t *)vb.p, other.dev_arena, (const int64_t *)vo.p, nk, dk);
+    hipLaunchKernelGGL(scatter_blocks_kernel, dim3((nk * D + 255) / 256), dim3(256), 0, s, (const double *)dk, (const int32_t *)dpos.p, nk, D, dperm);
+    so->ltx_norm2(s, dperm, out, 3);
+    // baseline: marginalised blocks first; log det of the marginal from the kept supernodes; selected inverse
+    if ((rc = sb->factorise(s, gbb, bad0))) return rc;
+    sb->logdiag(s, n_marg_sn, out, 2);
+    if ((rc = sb->selected_inverse(s, bad0))) return rc;
+    // trace(Sigma_kept Lambda_x): the sparsified graph's Hessian blocks against the selected inverse
+    const TraceSink ts{FrontSink{sb->dev, bad0}, (double *)tpart.p, 0.0};
+    by_dim(D, [&](auto d) { launch_assemble_into<decltype(d)::value>(gbx, ts, s, nullptr); });
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)tpart.p, other_.nv, out, 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(timer.stop(s));
+    int h_bad[2] = {0, 0};
+    double h_out[4] = {0, 0, 0, 0};
+    float ms = 0;
     HIPCHK(hipMemcpyAsync(h_out, outb.p, 4 * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (h_bad[0] == 2) { snprintf(err, errlen, "sparse KLD: an edge of the sparsified graph lies outside the fill of the baseline's marginal"); rc = SPG_ESTATE; goto done; }
+    HIPCHK(timer.ms(ms));
+    if (h_bad[0] == 2) { snprintf(err, errlen, "sparse KLD: an edge of the sparsified graph lies outside the fill of the baseline's marginal"); return SPG_ESTATE; }
     if (h_bad[0] || h_bad[1]) {
         snprintf(err, errlen, "global KLD: %s information matrix is not positive definite", h_bad[0] ? "the baseline" : "the sparsified");
-        rc = SPG_ENOTPD;
-        goto done;
+        return SPG_ENOTPD;
     }
-    {
-        const double n_keep = (double)D * nk;
-        const double innerprod = h_out[0], logdetx = 2 * h_out[1], logdety = -2 * h_out[2], mahal = h_out[3];
-        terms[0] = 0.5 * (innerprod + mahal - logdetx - logdety - n_keep);
-        terms[1] = innerprod; terms[2] = mahal; terms[3] = logdetx; terms[4] = logdety; terms[5] = n_keep;
-        if (seconds) *seconds = 1e-3 * ms;
-    }
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    const double n_keep = (double)D * nk;
+    const double innerprod = h_out[0], logdetx = 2 * h_out[1], logdety = -2 * h_out[2], mahal = h_out[3];
+    terms.kld = 0.5 * (innerprod + mahal - logdetx - logdety - n_keep);
+    terms.innerprod = innerprod; terms.mahalanobis = mahal; terms.logdetx = logdetx; terms.logdety = logdety; terms.n = (int64_t)n_keep;
+    terms.device_seconds += 1e-3 * ms;
+    return 0;
 }
 
 // Covariance blocks of a staged graph (in.pos >= 0: its free vertices, ascending = the block numbering) from the selected
 // inverse over its own plan: no marginalised part, so the item lists of the top-down recurrence cover every supernode
 // and the Z blocks take sum NP^2 over all of them. req: n requests of K vertex indices (-1 = zero rows and columns);
 // the blocks land in d_out (device, n (K D)^2 doubles). The fronts are released on return, before a caller factorises
-// a second graph. info[4] += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops;
-// *seconds += HIP-event time of assembly, factorisation, selected inverse and extraction.
-static int sigma_blocks(hipStream_t s, const DenseGraphIn &in_, int K, const int32_t *req, int n, double *d_out, double *seconds, double *info,
+// a second graph. stats += supernodes, bytes of fronts and Z blocks, factorisation flops, selected-inverse flops and the
+// HIP-event time of assembly, factorisation, selected inverse and extraction.
+static int sigma_blocks(hipStream_t s, const DenseGraphIn &in_, int K, const int32_t *req, int n, double *d_out, spg_cov_stats &stats,
                         char *err, size_t errlen) {
     const int D = in_.D;
     int rc = 0;
@@ -1467,62 +1457,52 @@ static int sigma_blocks(hipStream_t s, const DenseGraphIn &in_, int K, const int
         if (req[i] >= 0 && rpos[i] < 0) { snprintf(err, errlen, "covariance blocks: a requested vertex is not a variable"); return SPG_ESTATE; }
     }
     auto sp = std::make_unique<SparseSolver>();
-    const int nsn = plan.nsn;
-    const double fflops = plan.flops;
     if ((rc = sp->init(std::move(plan), true, err, errlen))) return rc;
-    if (info) { info[0] += nsn; info[1] += (double)(sp->plan.pool + sp->zpool_len) * 8; info[2] += fflops; info[3] += sp->selinv_flops; }
+    sp->count_into(stats);
     DenseGraphIn in = in_;
     in.pos = pos.data();
     GraphBufs gb;
     DevBuf bad, dreq;
-    int h_bad[2] = {0, 0};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
     HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    EventTimer timer;
     if ((rc = upload(dreq, rpos.data(), rpos.size(), s)) || (rc = stage_graph(in, gb, s))) {
         snprintf(err, errlen, "staging the graph for the covariance blocks failed (%d)", rc);
-        goto done;
+        return rc;
     }
     HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
-    HIPCHK(hipEventRecord(e0, s));
-    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); goto done; }
-    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); goto done; }
+    HIPCHK(timer.start(s));
+    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); return rc; }
+    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); return rc; }
     if (n > 0) {
         const FrontSink fs{sp->dev, (int *)bad.p + 1};
         const int32_t *rq = (const int32_t *)dreq.p;
-        if (D == 6 && K == 1) hipLaunchKernelGGL((sp_sigma_blocks_kernel<6, 1>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
-        else if (D == 6) hipLaunchKernelGGL((sp_sigma_blocks_kernel<6, 2>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
-        else if (K == 1) hipLaunchKernelGGL((sp_sigma_blocks_kernel<3, 1>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
-        else hipLaunchKernelGGL((sp_sigma_blocks_kernel<3, 2>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out);
+        by_dim(D, [&](auto d) {
+            auto launch = [&](auto k) { hipLaunchKernelGGL((sp_sigma_blocks_kernel<decltype(d)::value, decltype(k)::value>), dim3(n), dim3(64), 0, s, fs, rq, n, d_out); };
+            if (K == 1) launch(std::integral_constant<int, 1>{});
+            else launch(std::integral_constant<int, 2>{});
+        });
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(timer.stop(s));
+    int h_bad[2] = {0, 0};
+    float ms = 0;
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (seconds) *seconds += 1e-3 * ms;
-    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
-    if (h_bad[1]) { snprintf(err, errlen, "covariance blocks: a requested pair lies outside the fronts of the factorisation"); rc = SPG_ESTATE; goto done; }
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    HIPCHK(timer.ms(ms));
+    stats.device_seconds += 1e-3 * ms;
+    return cov_bad_flags(h_bad, err, errlen);
 }
 
-int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, double *seconds, double *info,
+int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int32_t *req, int n, double *out, spg_cov_stats &stats,
                           char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     const int W = K * in.D;
     const size_t len = (size_t)std::max(n, 1) * W * W;
-    int rc = 0;
     DevBuf dout;
     HIPCHK(hipMalloc(&dout.p, len * 8));
-    if ((rc = sigma_blocks(s, in, K, req, n, (double *)dout.p, seconds, info, err, errlen))) goto done;
+    if (int rc = sigma_blocks(s, in, K, req, n, (double *)dout.p, stats, err, errlen)) return rc;
     if (n > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)n * W * W * 8, hipMemcpyDeviceToHost));
-done:
-    return rc;
+    return 0;
 }
 
 // Covariance sub-blocks of arbitrary vertex pairs (spg_graph_pair_covariances / _joint_marginal_covariance). Sub-block i
@@ -1531,7 +1511,7 @@ done:
 // through the solves as well); the others take one column solve per pair of vertices, shared by (a, b) and (b, a).
 // Order on the device: factorisation, column solves on the intact factor, selected inverse, one assembly launch.
 int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
-                         int64_t out_len, double *out, double *seconds, double *info, char *err, size_t errlen) {
+                         int64_t out_len, double *out, spg_cov_solve_stats &stats, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     const int D = in_.D;
     const bool force = cov_force_solve();
@@ -1545,8 +1525,6 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *v
             return SPG_ESTATE;
         }
     auto sp = std::make_unique<SparseSolver>();
-    const int nsn = plan.nsn, nblocks = plan.n;
-    const double fflops = plan.flops;
     if ((rc = sp->init(std::move(plan), true, err, errlen))) return rc;
     const Plan &P = sp->plan;
     // sub-blocks -> selected inverse or a cross block; one cross block per unordered pair of positions
@@ -1567,7 +1545,7 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *v
         }
     }
     std::vector<int32_t> ccol, crow(cx.size());
-    choose_columns(nblocks, cx, cy, ccol);
+    choose_columns(P.n, cx, cy, ccol);
     for (size_t i = 0; i < cx.size(); i++) crow[i] = ccol[i] == cx[i] ? cy[i] : cx[i];
     for (CovBlk &b : blks)   // the cross block holds Sigma(row, column): transposed when a is the solved column
         if (b.cross >= 0) b.tr = (b.pa / D == ccol[b.cross] && b.pa != b.pb) ? 1 : 0;
@@ -1577,113 +1555,95 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *v
     GraphBufs gb;
     DevBuf bad, dout, dcross, dblk;
     int h_bad[2] = {0, 0};
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
     float ms0 = 0, ms1 = 0;
     HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
     HIPCHK(hipMalloc(&dout.p, (size_t)std::max<int64_t>(out_len, 1) * 8));
     HIPCHK(hipMalloc(&dcross.p, std::max<size_t>(cx.size(), 1) * D * D * 8));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventCreate(&e2));
-    HIPCHK(hipEventCreate(&e3));
+    EventTimer t_factor, t_selinv;   // the column solves in between keep their own time (ColumnSolves::seconds)
     if ((rc = upload(dblk, blks.data(), blks.size(), s)) || (rc = stage_graph(in, gb, s))) {
         snprintf(err, errlen, "staging the graph for the covariance blocks failed (%d)", rc);
-        goto done;
+        return rc;
     }
     HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
-    HIPCHK(hipEventRecord(e0, s));
-    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); goto done; }
-    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(t_factor.start(s));
+    if ((rc = sp->factorise(s, gb, (int *)bad.p))) { snprintf(err, errlen, "sparse assembly failed"); return rc; }
+    HIPCHK(t_factor.stop(s));
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
-    HIPCHK(hipEventElapsedTime(&ms0, e0, e1));
-    if ((rc = cs.run(s, (double *)dcross.p, err, errlen))) goto done;
-    HIPCHK(hipEventRecord(e2, s));
-    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); goto done; }
+    if (h_bad[0]) return cov_bad_flags(h_bad, err, errlen);
+    HIPCHK(t_factor.ms(ms0));
+    if ((rc = cs.run(s, (double *)dcross.p, err, errlen))) return rc;
+    HIPCHK(t_selinv.start(s));
+    if ((rc = sp->selected_inverse(s, (int *)bad.p))) { snprintf(err, errlen, "selected inverse failed"); return rc; }
     if (nblk > 0) {
         const FrontSink fs{sp->dev, (int *)bad.p + 1};
-        const dim3 g((unsigned)((nblk + 3) / 4)), b(256);
-        if (D == 6) hipLaunchKernelGGL((sp_cov_assemble_kernel<6>), g, b, 0, s, fs, (const CovBlk *)dblk.p, (int)nblk, (const double *)dcross.p, (double *)dout.p);
-        else hipLaunchKernelGGL((sp_cov_assemble_kernel<3>), g, b, 0, s, fs, (const CovBlk *)dblk.p, (int)nblk, (const double *)dcross.p, (double *)dout.p);
+        by_dim(D, [&](auto d) {
+            hipLaunchKernelGGL((sp_cov_assemble_kernel<decltype(d)::value>), dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, fs, (const CovBlk *)dblk.p, (int)nblk,
+                               (const double *)dcross.p, (double *)dout.p);
+        });
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e3, s));
+    HIPCHK(t_selinv.stop(s));
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ms1, e2, e3));
-    if (h_bad[0]) { snprintf(err, errlen, "covariance blocks: the information matrix is not positive definite"); rc = SPG_ENOTPD; goto done; }
-    if (h_bad[1]) { snprintf(err, errlen, "covariance blocks: a requested pair lies outside the fronts of the factorisation"); rc = SPG_ESTATE; goto done; }
+    HIPCHK(t_selinv.ms(ms1));
+    if ((rc = cov_bad_flags(h_bad, err, errlen))) return rc;
     if (out_len > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)out_len * 8, hipMemcpyDeviceToHost));
-    if (seconds) *seconds += 1e-3 * (ms0 + ms1) + cs.seconds;
-    if (info) {
-        info[0] += nsn; info[1] += (double)(P.pool + sp->zpool_len) * 8; info[2] += fflops; info[3] += sp->selinv_flops;
-        info[4] += (double)cs.cols.size(); info[5] += cs.nbatch; info[6] += cs.flops; info[7] += cs.seconds;
-    }
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e2) (void)hipEventDestroy(e2);
-    if (e3) (void)hipEventDestroy(e3);
-    return rc;
+    sp->count_into(stats.cov);
+    stats.cov.device_seconds += 1e-3 * (ms0 + ms1) + cs.seconds;
+    stats.columns += (int32_t)cs.cols.size(); stats.rhs_batches += cs.nbatch; stats.solve_flops += cs.flops; stats.solve_seconds += cs.seconds;
+    return 0;
 }
 
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,
-                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, double *seconds, double *info, char *err, size_t errlen) {
+                            const int64_t *vpo_base, const int64_t *vpo_other, double *kld, spg_cov_stats &stats, char *err, size_t errlen) {
     hipStream_t s = (hipStream_t)stream;
     const int D = base.D;
     const size_t len = (size_t)std::max(nk, 1) * D * D;
-    int rc = 0, h_bad[2] = {0, 0};
+    int rc = 0;
     DevBuf sy, sx, diff, dk, bad, pb, po;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
     HIPCHK(hipMalloc(&sy.p, len * 8));
     HIPCHK(hipMalloc(&sx.p, len * 8));
     HIPCHK(hipMalloc(&diff.p, (size_t)std::max(nk, 1) * D * 8));
     HIPCHK(hipMalloc(&dk.p, (size_t)std::max(nk, 1) * 8));
     HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    EventTimer timer;
     // one graph after the other: the baseline's fronts are gone before the sparsified graph is factorised
-    if ((rc = sigma_blocks(s, base, 1, vb, nk, (double *)sy.p, seconds, info, err, errlen))) {
+    if ((rc = sigma_blocks(s, base, 1, vb, nk, (double *)sy.p, stats, err, errlen))) {
         if (rc == SPG_ENOTPD) snprintf(err, errlen, "marginal KLD: the baseline information matrix is not positive definite");
-        goto done;
+        return rc;
     }
-    if ((rc = sigma_blocks(s, other, 1, vo, nk, (double *)sx.p, seconds, info, err, errlen))) {
+    if ((rc = sigma_blocks(s, other, 1, vo, nk, (double *)sx.p, stats, err, errlen))) {
         if (rc == SPG_ENOTPD) snprintf(err, errlen, "marginal KLD: the sparsified information matrix is not positive definite");
-        goto done;
+        return rc;
     }
     if ((rc = upload(pb, vpo_base, (size_t)nk, s)) || (rc = upload(po, vpo_other, (size_t)nk, s))) {
         snprintf(err, errlen, "staging the pose offsets for the marginal KLD failed (%d)", rc);
-        goto done;
+        return rc;
     }
     HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(int), s));
-    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(timer.start(s));
     if (nk > 0) {
-        const dim3 g((nk + 63) / 64), b(64);
-        if (D == 6) {
-            hipLaunchKernelGGL((pose_diff_kernel<6>), g, b, 0, s, (const double *)base.dev_arena, (const int64_t *)pb.p, (const double *)other.dev_arena, (const int64_t *)po.p, nk, (double *)diff.p);
-            hipLaunchKernelGGL((sp_marginal_kld_kernel<6>), g, b, 0, s, (const double *)sx.p, (const double *)sy.p, (const double *)diff.p, nk, (double *)dk.p, (int *)bad.p);
-        } else {
-            hipLaunchKernelGGL((pose_diff_kernel<3>), g, b, 0, s, (const double *)base.dev_arena, (const int64_t *)pb.p, (const double *)other.dev_arena, (const int64_t *)po.p, nk, (double *)diff.p);
-            hipLaunchKernelGGL((sp_marginal_kld_kernel<3>), g, b, 0, s, (const double *)sx.p, (const double *)sy.p, (const double *)diff.p, nk, (double *)dk.p, (int *)bad.p);
-        }
+        launch_pose_diff(D, s, base.dev_arena, (const int64_t *)pb.p, other.dev_arena, (const int64_t *)po.p, nk, (double *)diff.p);
+        by_dim(D, [&](auto d) {
+            hipLaunchKernelGGL((sp_marginal_kld_kernel<decltype(d)::value>), dim3((nk + 63) / 64), dim3(64), 0, s, (const double *)sx.p, (const double *)sy.p, (const double *)diff.p, nk,
+                               (double *)dk.p, (int *)bad.p);
+        });
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(timer.stop(s));
+    int h_bad[2] = {0, 0};
+    float ms = 0;
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     if (nk > 0) HIPCHK(hipMemcpyAsync(kld, dk.p, (size_t)nk * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (seconds) *seconds += 1e-3 * ms;
+    HIPCHK(timer.ms(ms));
+    stats.device_seconds += 1e-3 * ms;
     if (h_bad[0] || h_bad[1]) {
         snprintf(err, errlen, "marginal KLD: a marginal covariance of the %s graph is not positive definite", h_bad[0] ? "baseline" : "sparsified");
-        rc = SPG_ENOTPD;
+        return SPG_ENOTPD;
     }
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    return 0;
 }
 
 }  // namespace spg

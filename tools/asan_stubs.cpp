@@ -22,8 +22,11 @@ int rccl_get_unique_id(void *, char *, size_t) { return SPG_ENODEV; }
 int rccl_comm_create(int, int, int, const void *, void **, char *, size_t) { return SPG_ENODEV; }
 int rccl_allgather_f64(void *, void *, int64_t, int64_t, void *, char *, size_t) { return SPG_ENODEV; }
 void rccl_comm_destroy(void *) {}
-int hip_dense_kld(void *, const DenseGraphIn &, const DenseGraphIn &, int, int, const int64_t *, const int64_t *, double *, double *, char *, size_t) { return SPG_ENODEV; }
-int hip_dense_optimize(void *, const DenseGraphIn &, int, int, double *, double *, char *, size_t) { return SPG_ENODEV; }
-int hip_sparse_optimize(void *, const DenseGraphIn &, int, int, double *, double *, double *, char *, size_t) { return SPG_ENODEV; }
-int hip_sparse_kld(void *, const DenseGraphIn &, const DenseGraphIn &, const uint8_t *, const int32_t *, const int32_t *, int, const int64_t *, const int64_t *, double *, double *, double *, char *, size_t) { return SPG_ENODEV; }
+int hip_dense_kld(void *, const DenseGraphIn &, const DenseGraphIn &, int, int, const int64_t *, const int64_t *, spg_kld_terms &, char *, size_t) { return SPG_ENODEV; }
+int hip_dense_optimize(void *, const DenseGraphIn &, int, int, spg_optimize_stats &, char *, size_t) { return SPG_ENODEV; }
+int hip_sparse_optimize(void *, const DenseGraphIn &, int, int, spg_optimize_stats &, char *, size_t) { return SPG_ENODEV; }
+int hip_sparse_kld(void *, const DenseGraphIn &, const DenseGraphIn &, const uint8_t *, const int32_t *, const int32_t *, int, const int64_t *, const int64_t *, spg_kld_terms &, char *, size_t) { return SPG_ENODEV; }
+int hip_sparse_cov_blocks(void *, const DenseGraphIn &, int, const int32_t *, int, double *, spg_cov_stats &, char *, size_t) { return SPG_ENODEV; }
+int hip_sparse_cov_solve(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, double *, spg_cov_solve_stats &, char *, size_t) { return SPG_ENODEV; }
+int hip_sparse_marginal_kld(void *, const DenseGraphIn &, const DenseGraphIn &, const int32_t *, const int32_t *, int, const int64_t *, const int64_t *, double *, spg_cov_stats &, char *, size_t) { return SPG_ENODEV; }
 }
