@@ -271,7 +271,7 @@ int spg_graph_marginalize_ranks(spg_graph *g, const int32_t *which, int n, const
 /* Which batches are sharded. Default policy (threshold < 0): a cost model — a batch is sharded when the modelled
  * device time of this rank's slice plus one exchange is below the modelled time of the whole batch on one GPU
  * (per-blanket chain latency ~ n^2.5, blankets resident per GPU from the LDS carve-up, exchange = latency + bytes /
- * link rate; constants in csrc/spg_host.cpp). spg_graph_set_shard_threshold(g, n >= 0) replaces it by "at least n
+ * link rate; constants in csrc/spg_host_rounds.cpp). spg_graph_set_shard_threshold(g, n >= 0) replaces it by "at least n
  * blankets" (0 = always; used by tests). */
 /* Which driver spg_graph_marginalize uses for a single-rank NFR Tree call at the stored estimates. Default (-1): the
  * streaming driver on the HIP backend (one blanket = one item of the persistent worker kernel's queue, committed as its

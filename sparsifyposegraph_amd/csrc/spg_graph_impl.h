@@ -1,5 +1,6 @@
-// csrc/spg_graph_impl.h — the device-resident pose graph as the host translation units see it (spg_host.cpp: graph,
-// scheduler, drivers; spg_host_global.cpp: the whole-graph entry points). Private: not part of include/spg.h.
+// csrc/spg_graph_impl.h — the device-resident pose graph as the host translation units see it (spg_host.cpp: contexts,
+// graph, I/O; spg_host_rounds.cpp: round scheduler and batch driver; spg_host_stream.cpp: streaming driver;
+// spg_host_global.cpp: the whole-graph entry points) and what they share. Private: not part of include/spg.h.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -29,6 +30,16 @@ inline double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+inline void cpu_pause() {
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
+}
+// one turn of a wait for another thread: pause, and give the core away once the wait has become long
+inline void spin_wait(uint32_t &spins) {
+    if (++spins > 4096) std::this_thread::yield();
+    else cpu_pause();
+}
 }  // namespace
 
 // Host mirror of the arena: grows without value-initialising (the regions the device produces are
@@ -283,7 +294,6 @@ struct spg_graph {
     std::vector<int32_t> s_newpending, s_B, s_centres, s_Dv, s_tmp, s_work, s_seen, s_hit, s_vix;
     std::vector<double> s_cost;
     std::vector<int> s_first;
-    std::vector<int64_t> s_chunk_len;
     // ---- streaming driver (stream_marginalize below): per-vertex / per-slot / per-position state, kept between calls
     static constexpr int kSOwn = 4, kSMaxV = 16, kSMaxE = 44;
     struct SSlot {                                    // one blanket in flight
@@ -312,7 +322,143 @@ inline int set_err(spg_ctx *c, int code, const char *fmt, const char *a = "") {
     return code;
 }
 
+// ---- what crosses a unit boundary (library-internal: none of it is part of the exported ABI)
 // spg_host.cpp
 int sync_host(spg_graph *g);     // pull device-only ranges into the host mirror
 int sync_device(spg_graph *g);   // push host-only tail to the device
 void canonicalize_edge_order(spg_graph *g);
+// The three above were already default-visibility symbols of the shared object; the ones below are shared for the first
+// time and stay hidden, so that the library's dynamic symbol list does not grow.
+#pragma GCC visibility push(hidden)
+int arena_ensure(spg_graph *g, int64_t need);
+int add_edge_idx(spg_graph *g, int kind, int nv, const int32_t *vix, int64_t off, int32_t len, int64_t key = -1);
+// spg_host_rounds.cpp
+void quiesce_submission(spg_graph *g);   // wait until the submission thread has handed over every batch in its queue
+// spg_host_stream.cpp
+// Runs the removal list of the open marginalisation (spg_graph_marginalize_begin) through the streaming driver.
+// Returns 0 = list exhausted, 1 = the rest of the list (g->pending from g->pend_head) is left to the batch driver
+// (a blanket the persistent worker does not take, arena full, or no streaming on this backend), < 0 error.
+int stream_marginalize(spg_graph *g, bool *started = nullptr);
+#pragma GCC visibility pop
+
+namespace {
+inline void next_stamp(spg_graph *g) {
+    if (g->vstamp.size() < g->vid.size()) g->vstamp.resize(g->vid.size(), 0);
+    if (g->estamp.size() < g->edges.size()) g->estamp.resize(g->edges.size(), 0);
+    g->stamp++;
+}
+
+// [lo, hi) of the arena was produced on the device: the host mirror does not hold it until sync_host
+inline void mark_stale(spg_graph *g, int64_t lo, int64_t hi) {
+    if (g->stale_hi <= g->stale_lo) { g->stale_lo = lo; g->stale_hi = hi; }
+    else { g->stale_lo = std::min(g->stale_lo, lo); g->stale_hi = std::max(g->stale_hi, hi); }
+}
+
+// the HIP backend keeps the text of its last error: make it the context's
+inline void copy_backend_error(spg_ctx *c) { snprintf(c->err, sizeof c->err, "%s", spg::hip_backend_error(&c->be)); }
+
+// ---- out records ----------------------------------------------------------------------------------------------
+// Word [5] of an out record against the tag of the launch that is to write it (include/spg.h at SPG_OUT_HDR): every
+// poller of a mailbox asks this and nothing else.
+enum MailState { MAIL_NOT_YET = 0, MAIL_READY = 1, MAIL_FINAL = 2 };
+inline MailState mail_state(double word, double tag) {
+    return word == SPG_READY_WORD(tag) ? MAIL_READY : word == SPG_FINAL_WORD(tag) ? MAIL_FINAL : MAIL_NOT_YET;
+}
+
+// (a full-format record comes from the device: nothing in it is used as an index before it has been checked)
+// nv = vertices of the blanket the record belongs to
+inline bool out_record_well_formed(const double *rec, const spg_blanket_desc &bd, int nv) {
+    const int n_new = (int)rec[4];
+    if (n_new < 0 || n_new > bd.n_new_max) return false;
+    int vsum = 0;
+    for (int e = 0; e < n_new; e++) {
+        const double nvd = rec[SPG_OUT_HDR + 4 * e + 3], reld = rec[SPG_OUT_HDR + 4 * e + 1], lend = rec[SPG_OUT_HDR + 4 * e + 2];
+        if (!(nvd >= 1 && nvd <= nv && reld >= 0 && lend >= 1 && reld + lend <= (double)bd.new_len)) return false;
+        for (int i = 0; i < (int)nvd; i++) { const double li = rec[SPG_OUT_HDR + 4 * bd.n_new_max + vsum + i]; if (!(li >= 0 && li < nv)) return false; }
+        vsum += (int)nvd;
+        if (vsum > bd.n_new_vert_max) return false;
+    }
+    return true;
+}
+// The new edges of a full-format record: fn(e, kind, rel, len, nv, lv) — record at new_off + rel, `len` doubles;
+// lv[0 .. nv) = the edge's vertices as indices into the blanket's vertex list.
+template <class F>
+inline void for_each_new_edge(const double *rec, int n_new, int n_new_max, F &&fn) {
+    const double *lv = rec + SPG_OUT_HDR + 4 * n_new_max;
+    for (int e = 0; e < n_new; e++) {
+        const double *t = rec + SPG_OUT_HDR + 4 * e;
+        const int nv = (int)t[3];
+        fn(e, (int)t[0], (int64_t)t[1], (int32_t)t[2], nv, lv);
+        lv += nv;
+    }
+}
+// The new edges of a compact record (the persistent worker's, flags bit 20, spg_kernels.hip publish()): pose-pose
+// edges only, endpoint pairs as 4-bit local indices, edge e in byte e of words [6] / [7]; their records lie back to
+// back at new_off. fn(e, la, lb).
+template <class F>
+inline void for_each_compact_edge(const double *rec, int n_new, F &&fn) {
+    uint64_t w[2];
+    memcpy(w, rec + 6, 16);
+    for (int e = 0; e < n_new; e++) {
+        const unsigned pr = (unsigned)(w[e >> 3] >> (8 * (e & 7))) & 0xffu;
+        fn(e, (int)(pr & 15u), (int)(pr >> 4));
+    }
+}
+
+// ---- blanket descriptors ----------------------------------------------------------------------------------------
+// most new edges / endpoints / record doubles a blanket with k kept vertices can emit
+inline void new_edge_budget(const spg_options &o, int d, int k, int32_t &n_new_max, int32_t &n_new_vert_max, int64_t &new_len) {
+    int ps = pose_stride(d);
+    if (o.algorithm == SPG_ALG_NFR) {
+        // pattern size (src/pseudo_chow_liu.cpp:33-87): a tree, or up to all pairs for Dense / Subgraph
+        n_new_max = std::max(k - 1, 0);
+        if (k > 2 && (o.topology == SPG_TOPO_DENSE || o.topology == SPG_TOPO_SUBGRAPH)) {
+            const int msub = (int)((1 + o.chord_ratio) * (k - 1)), all = k * (k - 1) / 2;
+            n_new_max = (o.topology == SPG_TOPO_DENSE || msub >= all) ? all : std::max(msub, k - 1);
+        }
+        n_new_vert_max = 2 * n_new_max;
+        new_len = (int64_t)n_new_max * (ps + info_len(d));
+        // correlated patterns: up to k - 1 measurements in all, possibly in one SPG_EDGE_MULTI record
+        if (k > 2 && (o.topology == SPG_TOPO_CLIQUEY_SUBGRAPH || o.topology == SPG_TOPO_CLIQUEY_DENSE)) new_len += SPG_MULTI_LEN(d, k - 1);
+    } else if (o.topology == SPG_TOPO_DENSE || k <= 1) {
+        int64_t n = (int64_t)d * k;
+        n_new_max = k > 0 ? 1 : 0;
+        n_new_vert_max = k;
+        new_len = n + n * n;
+    } else {
+        int64_t n2 = 2 * d;
+        n_new_max = k;
+        n_new_vert_max = 2 * k - 1;
+        new_len = (d + (int64_t)d * d) + (int64_t)(k - 1) * (n2 + n2 * n2);
+    }
+}
+
+// Appends the input side of one blanket's descriptor to a round's host arrays: its vertices' poses (verts: removed
+// first, then kept), its edges' records and their vertices as indices into `verts` (through g->lidx, which must cover
+// every vertex), and the assembly scratch its n-ary edges need. The output side of bd (new-edge budget, out_off /
+// new_off) is the region layout's and stays with the caller. Reads only what no commit changes while the blanket is
+// open: poses' offsets, the location / endpoints of existing edges.
+inline void append_blanket_desc(spg_graph *g, const int32_t *verts, int nv, int n_remove, const int32_t *eids, int ne,
+                                spg_blanket_desc &bd, std::vector<int64_t> &h_vpo, std::vector<spg_edge_ref> &h_er, std::vector<int32_t> &h_ev) {
+    const int d = g->d;
+    int32_t *const lidx = g->lidx.data();
+    memset(&bd, 0, sizeof bd);
+    bd.vert_begin = (int32_t)h_vpo.size();
+    bd.n_vert = nv;
+    bd.n_remove = n_remove;
+    for (int i = 0; i < nv; i++) { h_vpo.push_back(g->vpose[verts[i]]); lidx[verts[i]] = (int32_t)i; }
+    bd.edge_begin = (int32_t)h_er.size();
+    bd.n_edge = ne;
+    int32_t scratch = 0;
+    for (int ei = 0; ei < ne; ei++) {
+        const GEdge &e = g->edges[eids[ei]];
+        if (e.kind == SPG_EDGE_GLC) scratch = std::max(scratch, e.len - d * e.nv + e.nv * 2 * d * d);
+        spg_edge_ref er;
+        er.off = e.off; er.len = e.len; er.kind = e.kind; er.vbegin = (int32_t)h_ev.size(); er.nv = e.nv;
+        for (int i = 0; i < e.nv; i++) h_ev.push_back(lidx[edge_verts(g, e)[i]]);
+        h_er.push_back(er);
+    }
+    bd.pad_ = scratch;  // doubles of assembly scratch the blanket's n-ary edges need (r*dq + q*2*d*d)
+    bd.tinfo_off = -1;
+}
+}  // namespace

@@ -1,4 +1,4 @@
-"""CPU: the streaming driver's selection rule and commit path (csrc/spg_host.cpp, `Streamer`) — one blanket = one item
+"""CPU: the streaming driver's selection rule and commit path (csrc/spg_host_stream.cpp, `Streamer`) — one blanket = one item
 handed to the device the moment the rule allows it, committed the moment its result arrives — driven through the C ABI
 with the oracle injected as the arithmetic and an EMULATED device that completes the blankets in flight in orders drawn
 from a seed (all oldest-first, or random subsets in random order). Whatever the completion order, the result must be

@@ -1,6 +1,6 @@
 // tools/host_sim.cpp — host-side timing of the streaming driver without a GPU.
 //
-// The driver of csrc/spg_host.cpp (selection rule, commit, packets, doorbells, mailbox polling) runs unchanged; behind
+// The driver of csrc/spg_host_stream.cpp (selection rule, commit, packets, doorbells, mailbox polling) runs unchanged; behind
 // it a thread of this tool plays the persistent worker kernel: it takes the queue items the driver publishes, waits a
 // fixed latency (the measured ticket -> ready word time of one blanket on MI355X) and writes the blanket's out record
 // and new edge records — recorded beforehand from the CPU oracle (test infrastructure, dlopen'ed here as such) — into

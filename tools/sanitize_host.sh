@@ -8,6 +8,7 @@ OUT=${TMPDIR:-/tmp}/spg_asan
 mkdir -p $OUT
 g++ -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -I$ROOT/sparsifyposegraph_amd/csrc \
     -shared -pthread -o $OUT/libspg_host_asan.so $ROOT/sparsifyposegraph_amd/csrc/spg_host.cpp \
+    $ROOT/sparsifyposegraph_amd/csrc/spg_host_rounds.cpp $ROOT/sparsifyposegraph_amd/csrc/spg_host_stream.cpp \
     $ROOT/sparsifyposegraph_amd/csrc/spg_host_global.cpp $ROOT/tools/asan_stubs.cpp
 cd $ROOT
 LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 \
