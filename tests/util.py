@@ -15,7 +15,8 @@ GAP_TOL = 1e-10
 
 def golden_cases():
     names = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
-    return [n for n in names if not n.startswith("digest_")]   # digests of full-size Dense runs: tests/golden/make_dense_digest.py
+    # digests of full-size Dense runs: tests/golden/make_dense_digest.py; geometry_cases: tests/golden/make_geometry_cases.py
+    return [n for n in names if not n.startswith("digest_") and n != "geometry_cases"]
 
 
 def load_golden(name):
