@@ -29,6 +29,7 @@
 #include "spg_dev_geom.hpp"
 #include "spg_dev_la.hpp"
 #include "spg_internal.h"
+#include "spg_hip_buffers.hpp"
 
 using namespace spgdev;
 
@@ -1140,10 +1141,7 @@ __global__ void big_out_record_kernel(double *orec, const int *flags, const doub
 }
 
 // ------------------------------------------------------------------------------------------ host side
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
+using spg::DevBuf;   // (spg_hip_buffers.hpp)
 
 // A span of stream work timed by a pair of HIP events: start(s) ... stop(s), and ms() once the stream is synchronised.
 struct EventTimer {

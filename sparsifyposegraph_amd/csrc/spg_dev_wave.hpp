@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "spg_dev_la.hpp"
+#include "spg_blanket_layout.hpp"   // kWaveMax: the largest n these kernels serve (the round planner needs it too)
 
 namespace spgdev {
 
@@ -155,10 +156,5 @@ __device__ __forceinline__ bool wave_spd_logdet(const double *src, int ld, int n
     if (n <= 12) return wave_spd_logdet_n<12>(src, ld, n, lane, logdet);
     return wave_spd_logdet_n<24>(src, ld, n, lane, logdet);
 }
-
-// N = 36 would serve k <= 6 (SE3) too, but its 72 live fp64 registers push the whole kernel to 256
-// VGPRs + scratch spills (rocprofv3: 8.3 MB of spill writes per 200-blanket launch); larger tiles use
-// the LDS-cooperative routines instead.
-constexpr int kWaveMax = 24;
 
 }  // namespace spgdev

@@ -8,7 +8,7 @@
 //   buildSubgraph's vertex ordering           src/vertex_remover.cpp:349-356
 //   updateInputGraph                          src/vertex_remover.cpp:500-546
 //   GraphWrapperG2O bookkeeping               src/graph_wrapper_g2o.cpp:207-247,398-453
-// Everything numeric runs in the HIP backend (spg_kernels.hip) on records that live in one HBM
+// Everything numeric runs in the HIP backend (spg_hip_backend.cpp, kernels in spg_kernels.hip) on records that live in one HBM
 // arena: [poses | edge records | per-round output regions]. The host keeps topology only.
 #include "spg_graph_impl.h"
 

@@ -1,5 +1,5 @@
-// csrc/spg_kernels.hip — the per-blanket marginalisation kernel for gfx950 and the HIP backend
-// that launches one conflict-free round of blankets.
+// csrc/spg_kernels.hip — the per-blanket marginalisation kernels for gfx950 and their launch entry points
+// (the HIP backend that plans and launches one conflict-free round of blankets is host code: spg_hip_backend.cpp).
 //
 // One workgroup per Markov blanket (64 lanes = one wavefront for blankets whose tiles fit in LDS,
 // 256 lanes with an L2-resident workspace for the rare large ones). The whole per-vertex iteration
@@ -22,14 +22,9 @@
 // the algorithmic minimum: every pose and edge record is read once, every new record written once.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <atomic>
-#include <chrono>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include <algorithm>
 #include "../../include/spg.h"
+#include "spg_blanket_layout.hpp"
 #include "spg_dev_geom.hpp"
 #include "spg_dev_la.hpp"
 #include "spg_dev_wave.hpp"
@@ -37,107 +32,9 @@
 
 using namespace spgdev;
 
+using spg::EC; using spg::SPG_ALG_NFR_LM; using spg::Layout; using spg::make_layout; using spg::KArgs;
+
 namespace {
-
-constexpr int EC = 8;  // edges whose Jacobians are staged per chunk
-// kernel-internal third value of the ALG template parameter: NFR with the blanket-level LM of the Local
-// linearisation point compiled in (its pose-update arithmetic costs ~160 VGPRs; the plain NFR kernel has 84)
-constexpr int SPG_ALG_NFR_LM = 2;
-
-// LDS / workspace carve-up for one blanket (all offsets in doubles). Monotone in k and m, so the
-// layout of the largest blanket of a launch bounds every blanket in it.
-struct Layout {
-    int n, nm, ld, ldm, P, NE;
-    int o_pose, o_red, o_cs, o_ev, o_S, o_w, o_ldb, o_Lb, o_nJ, o_X, o_eJ, o_eO, o_eT, o_Ng, o_tre, o_xch, o_int, small_doubles;
-    int o_M1, o_M2, o_M3, o_Hmm, o_Hmk, mat_doubles;
-    // int area offsets (in ints, relative to o_int)
-    int i_perm, i_keep, i_sorted, i_pij, i_comp, i_pairs, i_ev, i_misc, int_count;
-    // GLC tail: CNT problems of size S (tree: k-1 of 2d; dense / k==1: one of n), see glc section
-    int gS, gCNT, gld, gstride;
-    int o_gmeas, o_gev, o_gcs, o_gscr;          // small (LDS)
-    int i_gperm, i_gdone, i_gmeta, i_gverts;    // ints
-    int o_G, o_gA;                              // mat space: 4 batch buffers; GLC-edge assembly scratch
-};
-
-__host__ __device__ inline Layout make_layout(int D, int nt, int k, int m, int alg = SPG_ALG_NFR, int topo = SPG_TOPO_TREE,
-                                              int scratch = 0) {
-    Layout L;
-    const bool glc = (alg == SPG_ALG_GLC);
-    const bool single = (topo == SPG_TOPO_DENSE) || k <= 1;
-    int DD = D * D;
-    L.n = D * k; L.nm = D * m;
-    L.ld = L.n | 1; L.ldm = L.nm | 1;
-    L.P = k * (k - 1) / 2;
-    L.NE = k > 0 ? k : 1;  // most new edges any algorithm emits (GLC tree: root + k-1)
-    int psz = (D == 6) ? 12 : 3;
-    int o = 0;
-    L.o_pose = o; o += (k + m) * psz;
-    L.o_red = o; o += nt;
-    L.o_cs = o; o += L.n + 4;
-    L.o_ev = o; o += L.n;
-    L.o_S = o; o += L.n;
-    L.o_w = o; o += (L.P > 0 ? L.P : 1);
-    L.o_ldb = o; o += k + 1;
-    L.o_Lb = o; o += k * DD;
-    L.o_nJ = o; o += L.NE * 2 * DD;
-    L.o_X = o; o += L.NE * DD;
-    L.o_eJ = o; o += EC * 2 * DD;
-    L.o_eO = o; o += EC * DD;
-    L.o_eT = o; o += EC * 2 * DD;
-    L.o_Ng = o; o += L.n * D;
-    L.o_tre = o; o += L.NE;
-    L.o_xch = o; o += 4;
-    L.gS = single ? (k > 0 ? D * k : D) : 2 * D;
-    L.gCNT = single ? 1 : (k - 1);
-    L.gld = L.gS | 1;
-    L.gstride = L.gS * L.gld;
-    L.o_gmeas = o; if (glc) o += L.gCNT * L.gS;
-    L.o_gev = o; if (glc) o += L.gCNT * L.gS;
-    L.o_gcs = o; if (glc) o += L.gCNT * (L.gS + 4);
-    L.o_gscr = o; if (glc) o += L.gCNT * (2 * L.gS + 2);
-    L.o_int = o;
-    int io = 0;
-    L.i_perm = io; io += L.n;
-    L.i_keep = io; io += L.n;
-    L.i_sorted = io; io += (L.P > 0 ? L.P : 1);
-    L.i_pij = io; io += 2 * (L.P > 0 ? L.P : 1);
-    L.i_comp = io; io += k + 1;
-    L.i_pairs = io; io += 2 * L.NE;
-    L.i_ev = io; io += 2 * EC;
-    L.i_misc = io; io += 12;
-    L.i_gperm = io; if (glc) io += L.gCNT * L.gS;
-    L.i_gdone = io; if (glc) io += L.gCNT;
-    L.i_gmeta = io; if (glc) io += 3 * (L.NE + 1);
-    L.i_gverts = io; if (glc) io += 2 * L.NE + k + 2;
-    L.int_count = io;
-    o += (io + 1) / 2;
-    L.small_doubles = o;
-    int mo = 0;
-    L.o_M1 = mo; mo += L.n * L.ld;
-    L.o_M2 = mo; mo += L.n * L.ld;
-    L.o_M3 = mo; mo += L.n * L.ld;
-    L.o_Hmm = mo; mo += L.nm * L.ldm;
-    L.o_Hmk = mo; mo += L.nm * L.ld;
-    L.o_G = mo; if (glc) mo += 4 * L.gCNT * L.gstride;
-    L.o_gA = mo; if (glc) mo += scratch;
-    L.mat_doubles = mo;
-    return L;
-}
-
-struct KArgs {
-    double *arena;
-    const spg_blanket_desc *blk;
-    const int64_t *vpo;
-    const spg_edge_ref *er;
-    const int32_t *ev;
-    const int32_t *list;
-    double *gws;
-    int64_t gws_stride;
-    int topology, algorithm, flags, lin_point, tag;
-    double chord_ratio;
-    double *mail;        // pinned host mailbox for out records (or nullptr)
-    int64_t mail_base;   // arena offset that maps to mail[0]
-};
 
 // A value every lane holds identically: pin it to scalar registers. The descriptor fields steer every loop bound and
 // tile offset of a blanket; where they arrive through LDS or a stack slot (persistent worker) the compiler would
@@ -1638,969 +1535,79 @@ __global__ void __launch_bounds__(128) blanket_worker(WorkQ *q, unsigned long lo
 
 }  // namespace
 
-// =================================================================================== HIP backend
+// =================================================================================== launch entry points
+// What the backend (spg_hip_backend.cpp, host-only code) calls to put these kernels on a stream. Which variant, how many
+// blocks and how much LDS is decided there (spg_round_plan.hpp); the timing events are the backend's as well.
 namespace spg {
 
-// (`err` is HipBackend::err, 512 bytes, as the member array or through a char * alias)
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, (size_t)512, "%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); return SPG_EHIP; } } while (0)
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(err, errlen, "%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); return SPG_EHIP; } } while (0)
 
-struct HipBackend {
-    int device = 0;
-    char err[512] = {0};
-    struct Timed { hipEvent_t a, b; double bytes; int blankets; };
-    // Independent launch slots (stream + descriptor buffers + pinned staging + pinned mailbox +
-    // large-blanket workspace) so that the host can prepare and launch one batch of blankets while the
-    // previous one is still running.
-    struct Slot {
-        hipStream_t stream = nullptr;
-        void *d_desc = nullptr, *d_gws = nullptr, *d_ipws = nullptr, *d_lpose = nullptr, *d_lmeta = nullptr;
-        size_t c_desc = 0, c_gws = 0, c_ipws = 0, c_lpose = 0, c_lmeta = 0;
-        void *h_mail = nullptr, *d_mail = nullptr;   // pinned host mailbox the kernel writes out records into
-        size_t c_mail = 0;
-        void *h_stage = nullptr;                      // pinned host staging for the descriptor upload
-        void *d_stage = nullptr;                      // the same buffer in the device's address space
-        size_t c_stage = 0;
-        bool busy = false;                            // work was queued on the stream since its last synchronisation
-        std::vector<int32_t> bin_lists[5];            // scratch of hip_run_round
-        // Waiting for a slot goes through the event recorded behind its last kernel: hipStreamSynchronize on
-        // a stream that ends in a kernel has to submit a marker first and was measured at ~10 us per call,
-        // hipEventSynchronize on an already recorded event at ~1 us.
-        hipEvent_t done = nullptr, wait_ev = nullptr;
-        void *d_bar = nullptr;                        // fine-grained device memory the host writes through the PCIe BAR
-        size_t c_bar = 0;
-        // blankets of the last batch that went through the persistent worker: addresses of their final words in the
-        // pinned mailbox (wait_slot polls them: the slot's buffers may be rewritten once all of them are final)
-        std::vector<const volatile double *> finals;
-        double final_word = 0;
-        void *d_pkt = nullptr;                        // fine-grained device memory for the packets (host writes, BAR)
-        size_t c_pkt = 0;
-        bool stream_dirty = false;                    // something was queued on `stream` since the last wait
-        std::vector<Timed> pending;
-        // per slot, so that a submission thread working on one slot and the graph thread draining
-        // another never share state
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-        double prof_ms = 0, prof_bytes = 0;
-        long long prof_launches = 0, prof_blankets = 0;
-    };
-    static constexpr int NSLOT = 8;
-    Slot slots[NSLOT];
-    // the persistent worker kernel (one per backend, alive between the first narrow batch of a marginalisation and
-    // the next full synchronisation)
-    struct Worker {
-        hipStream_t stream = nullptr;
-        WorkQ *q = nullptr;                           // fine-grained device memory; the host stores through the BAR
-        unsigned long long *ticket = nullptr;         // device memory
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;
-        bool running = false, disabled = false;
-        int D = 0, alg = 0;
-        unsigned long long tail = 0;                  // host copy of q->tail
-        double bytes = 0;                             // algorithmic bytes / blankets handed over since it started
-        long long blankets = 0;
-        int bells = 1, lazy = 0;                     // (more doorbell copies / lazier polls: measured, no effect)
-        int wgs = 256;                                // one per CU: launched kernels must always find room next to it
-        std::chrono::steady_clock::time_point last_push;
-    } worker;
-    int batches_in_call = 0;                          // batches since the last full synchronisation
-    // streaming driver (hip_stream_open): its own packet ring (fine-grained device memory) and pinned mailbox
-    void *st_pkt = nullptr, *st_hmail = nullptr, *st_dmail = nullptr;
-    size_t c_st_pkt = 0, c_st_mail = 0;
-    int worker_cooldown = 0;                          // batches to go before the worker is considered again
-    double prof_big_ms = 0, prof_big_flops = 0;       // large-blanket dense pipeline (always accumulated)
-    long long prof_big_count = 0;
-    int prof_big_nmax = 0;
-    double prof_worker_ms = 0, prof_worker_bytes = 0;
-    long long prof_worker_runs = 0, prof_worker_blankets = 0;
-    int lds_limit = 160 * 1024;
-    bool large_bar = false;       // the host can store straight into device memory (hipDeviceAttributeIsLargeBar)
-    std::atomic<int> n_launches{0};
-    bool force_one_wave = false;  // SPG_ONE_WAVE=1: never use the two-wavefront latency variant (A/B timing)
-    // optional per-launch timing with HIP events on the launch stream (bench.py roofline leg)
-    bool profiling = false;
-    int prof_stride = 1, prof_tick = 0;   // time every prof_stride-th launch (1 = all)
+// (the worker first, then the blanket variants, then the pre-pass: the order the kernels have in the code object)
+namespace {
+template <int D>
+int launch_worker(int grid, size_t lds, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b, WorkQ *q, unsigned long long *ticket, long long idle_ticks,
+                  int bells, int lazy, char *err, size_t errlen) {
+    auto kern = blanket_worker<D, SPG_ALG_NFR>;
+    if (lds > 48 * 1024)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(128), (uint32_t)lds, s, ev_a, ev_b, 0, q, ticket, idle_ticks, bells, lazy);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}  // namespace
 
-    int ensure(Slot &S, void **p, size_t *cap, size_t need) {
-        if (need <= *cap) return 0;
-        size_t nc = std::max(need, *cap * 2);
-        if (*p) { if (int rc = worker_stop()) return rc; HIPCHK(hipStreamSynchronize(S.stream)); HIPCHK(hipFree(*p)); *p = nullptr; }
-        HIPCHK(hipMalloc(p, nc));
-        *cap = nc;
-        return 0;
-    }
-    int wait_slot(Slot &S) {
-        if (S.wait_ev) { HIPCHK(hipEventSynchronize(S.wait_ev)); S.wait_ev = nullptr; }
-        else if (S.stream_dirty) HIPCHK(hipStreamSynchronize(S.stream));
-        S.stream_dirty = false;
-        if (!S.finals.empty()) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (const volatile double *p : S.finals) {
-                uint32_t spins = 0;
-                while (*p != S.final_word) {
-                    if ((++spins & 0xfff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0) {
-                        snprintf(err, sizeof err, "persistent worker: a blanket did not complete within 10 s");
-                        return SPG_EHIP;
-                    }
-#if defined(__x86_64__)
-                    __builtin_ia32_pause();
-#endif
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-            S.finals.clear();
-        }
-        S.busy = false;
-        return 0;
-    }
-    int worker_stop();
-    int worker_start(int D, int alg);
-    int ensure_stage(Slot &S, size_t need) {
-        if (need <= S.c_stage) return 0;
-        size_t nc = std::max(need, S.c_stage * 2);
-        if (S.h_stage) { if (int rc = worker_stop()) return rc; HIPCHK(hipStreamSynchronize(S.stream)); HIPCHK(hipHostFree(S.h_stage)); S.h_stage = nullptr; }
-        HIPCHK(hipHostMalloc(&S.h_stage, nc, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(&S.d_stage, S.h_stage, 0));
-        S.c_stage = nc;
-        return 0;
-    }
-};
+int hip_worker_launch(int D, int grid, size_t lds_bytes, void *stream, void *ev_start, void *ev_stop, WorkQ *q, unsigned long long *ticket,
+                      long long idle_ticks, int bells, int lazy, char *err, size_t errlen) {
+    if (D == 6) return launch_worker<6>(grid, lds_bytes, (hipStream_t)stream, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, q, ticket, idle_ticks, bells, lazy, err, errlen);
+    if (D == 3) return launch_worker<3>(grid, lds_bytes, (hipStream_t)stream, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, q, ticket, idle_ticks, bells, lazy, err, errlen);
+    snprintf(err, errlen, "no worker kernel for D=%d", D);
+    return SPG_EINVAL;
+}
 
+namespace {
 template <int D, int NT, bool GWS, int ALG>
-static int launch_bin(HipBackend *hb, HipBackend::Slot &S, const KArgs &ka, int nblocks, size_t lds_bytes, double alg_bytes) {
-    char *err = hb->err;
+int launch_variant(hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, const KArgs &ka, int nblocks, size_t lds_bytes, char *err, size_t errlen) {
     auto kern = blanket_kernel<D, NT, GWS, ALG>;
     if (lds_bytes > 64 * 1024)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    HipBackend::Timed t{};
-    const bool timed = hb->profiling && (hb->prof_tick++ % hb->prof_stride == 0);
-    if (timed) {
-        if (S.pool.empty()) {
-            HIPCHK(hipEventCreate(&t.a));
-            HIPCHK(hipEventCreate(&t.b));
-        } else { t.a = S.pool.back().first; t.b = S.pool.back().second; S.pool.pop_back(); }
-        t.bytes = alg_bytes; t.blankets = nblocks;
-        // one runtime call: the dispatch itself carries the two events (start / stop of this kernel)
-        hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(NT), (uint32_t)lds_bytes, S.stream, t.a, t.b, 0, ka);
-        HIPCHK(hipGetLastError());
-        S.pending.push_back(t);
-        S.wait_ev = t.b;
-    } else {
-        hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(NT), (uint32_t)lds_bytes, S.stream, nullptr, S.done, 0, ka);
-        HIPCHK(hipGetLastError());
-        S.wait_ev = S.done;
-    }
-    hb->n_launches++;
-    S.stream_dirty = true;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------- worker control (host)
-static inline void bar_fence() {
-    std::atomic_thread_fence(std::memory_order_release);
-#if defined(__x86_64__)
-    __builtin_ia32_sfence();   // write-combining buffers drained: stores through the BAR leave in program order
-#endif
-}
-
-template <int D, int ALG>
-static int launch_worker(HipBackend *hb, size_t lds) {
-    char *err = hb->err;
-    auto kern = blanket_worker<D, ALG>;
-    if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long idle_ticks = 10LL * 100000000LL;   // 10 s of the 100 MHz wall clock
-    hipExtLaunchKernelGGL(kern, dim3(hb->worker.wgs), dim3(128), (uint32_t)lds, hb->worker.stream, hb->worker.ev_a, hb->worker.ev_b, 0,
-                          hb->worker.q, hb->worker.ticket, idle_ticks, hb->worker.bells, hb->worker.lazy);
+    // one runtime call: the dispatch itself carries the two events (start / stop of this kernel)
+    hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(NT), (uint32_t)lds_bytes, s, ev_start, ev_stop, 0, ka);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int HipBackend::worker_start(int D, int alg) {
-    Worker &W = worker;
-    if (W.running && W.D == D && W.alg == alg) {
-        // an idle worker leaves by itself after 10 s without a new item (every wave needs an exit the host cannot
-        // withhold): after a pause of more than 1 s retire it and start a fresh one rather than trust a half-gone grid
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - W.last_push).count() < 1.0) return 0;
-    }
-    if (W.running) if (int rc = worker_stop()) return rc;
-    if (!W.stream) {
-        HIPCHK(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreate(&W.ev_a));
-        HIPCHK(hipEventCreate(&W.ev_b));
-        if (hipExtMallocWithFlags((void **)&W.q, sizeof(WorkQ), hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); W.disabled = true; return 1; }
-        HIPCHK(hipMalloc((void **)&W.ticket, 64));
-        const char *e = getenv("SPG_WORKER_WGS");
-        if (e && atoi(e) > 0) W.wgs = atoi(e);
-        if ((e = getenv("SPG_WORKER_BELLS")) && atoi(e) >= 1 && atoi(e) <= kBells) W.bells = atoi(e);
-        if ((e = getenv("SPG_WORKER_LAZY")) && atoi(e) >= 0) W.lazy = atoi(e);
-    }
-    for (int c = 0; c < W.bells; c++) W.q->tail[c * kBellStride] = 0;     // through the BAR
-    W.q->stop = 0;
-    bar_fence();
-    W.tail = 0; W.bytes = 0; W.blankets = 0;
-    HIPCHK(hipMemsetAsync(W.ticket, 0, 64, W.stream));
-    // LDS of the largest blanket a worker takes: n <= kWaveMax, one removed vertex, the two-wavefront carve-up
-    Layout L = make_layout(D, 128, kWorkerMaxN / D, 1, alg, SPG_TOPO_TREE, 0);
-    const size_t lds = (size_t)(L.small_doubles + L.mat_doubles) * 8;
-    int rc = (D == 6) ? launch_worker<6, SPG_ALG_NFR>(this, lds) : launch_worker<3, SPG_ALG_NFR>(this, lds);
-    if (rc) return rc;
-    W.running = true; W.D = D; W.alg = alg;
-    W.last_push = std::chrono::steady_clock::now();
-    n_launches++;
+// every instantiation of blanket_kernel there is, for both pose dimensions
+struct VariantRow {
+    BlanketVariant v;
+    int (*launch)(hipStream_t, hipEvent_t, hipEvent_t, const KArgs &, int, size_t, char *, size_t);
+};
+#define SPG_VARIANT(NT, GWS, ALG) {{6, NT, GWS, ALG}, launch_variant<6, NT, GWS, ALG>}, {{3, NT, GWS, ALG}, launch_variant<3, NT, GWS, ALG>}
+const VariantRow kVariants[] = {
+    SPG_VARIANT(128, false, SPG_ALG_NFR_LM), SPG_VARIANT(128, false, SPG_ALG_NFR), SPG_VARIANT(256, false, SPG_ALG_NFR),
+    SPG_VARIANT(64, false, SPG_ALG_GLC),     SPG_VARIANT(64, false, SPG_ALG_NFR_LM), SPG_VARIANT(64, false, SPG_ALG_NFR),
+    SPG_VARIANT(256, true, SPG_ALG_GLC),     SPG_VARIANT(256, true, SPG_ALG_NFR_LM), SPG_VARIANT(1024, true, SPG_ALG_NFR),
+    SPG_VARIANT(256, true, SPG_ALG_NFR),
+};
+#undef SPG_VARIANT
+}  // namespace
+
+int hip_blanket_launch(const BlanketVariant &v, void *stream, void *ev_start, void *ev_stop, const KArgs &ka, int nblocks, size_t lds_bytes,
+                       char *err, size_t errlen) {
+    for (const VariantRow &r : kVariants)
+        if (r.v.D == v.D && r.v.NT == v.NT && r.v.gws == v.gws && r.v.alg == v.alg)
+            return r.launch((hipStream_t)stream, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ka, nblocks, lds_bytes, err, errlen);
+    snprintf(err, errlen, "no blanket kernel for D=%d with %d lanes, %s tiles, algorithm %d", v.D, v.NT, v.gws ? "workspace" : "LDS", v.alg);
+    return SPG_EINVAL;
+}
+
+int hip_local_point_launch(int D, void *stream, int count, const double *arena, double *lpose, const spg_blanket_desc *blk, const int64_t *vpo,
+                           const spg_edge_ref *er, const int32_t *ev, const int32_t *list, const int64_t *lp_off, int32_t *flag, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    if (D == 6) hipLaunchKernelGGL((local_point_kernel<6>), dim3((unsigned)count), dim3(64), 0, s, arena, lpose, blk, vpo, er, ev, list, lp_off, flag);
+    else if (D == 3) hipLaunchKernelGGL((local_point_kernel<3>), dim3((unsigned)count), dim3(64), 0, s, arena, lpose, blk, vpo, er, ev, list, lp_off, flag);
+    else { snprintf(err, errlen, "no local-point kernel for D=%d", D); return SPG_EINVAL; }
+    HIPCHK(hipGetLastError());
     return 0;
-}
-
-int HipBackend::worker_stop() {
-    Worker &W = worker;
-    if (!W.running) return 0;
-    W.q->stop = 1;
-    bar_fence();
-    HIPCHK(hipStreamSynchronize(W.stream));
-    W.running = false;
-    if (profiling) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, W.ev_a, W.ev_b) == hipSuccess) {
-            prof_worker_ms += ms; prof_worker_bytes += W.bytes; prof_worker_runs++; prof_worker_blankets += W.blankets;
-        }
-    }
-    return 0;
-}
-
-static void drain_profile(HipBackend *hb, HipBackend::Slot &S) {
-    for (auto &t : S.pending) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
-            S.prof_ms += ms; S.prof_bytes += t.bytes; S.prof_launches++; S.prof_blankets += t.blankets;
-        }
-        S.pool.push_back({t.a, t.b});
-    }
-    S.pending.clear();
-}
-
-#ifdef SPG_LAUNCH_PROF
-static double lp_t[6]; static long lp_n;
-#define LP(i) do { auto n_ = std::chrono::steady_clock::now(); lp_t[i] += std::chrono::duration<double, std::micro>(n_ - lp0_).count(); lp0_ = n_; } while (0)
-#define LP0 auto lp0_ = std::chrono::steady_clock::now(); lp_n++
-#else
-#define LP(i) do {} while (0)
-#define LP0 do {} while (0)
-#endif
-static int hip_run_round(void *user, void *arena, const spg_round_desc *rd) {
-    HipBackend *hb = (HipBackend *)user;
-    LP0;
-    char *err = hb->err;
-    if (rd->count <= 0) return 0;
-    HipBackend::Slot &S = hb->slots[rd->slot & (HipBackend::NSLOT - 1)];
-    const spg_options &o = *rd->opts;
-    const int D = o.pose_dim;
-    if (D != 3 && D != 6) return SPG_EINVAL;
-    // (the worker decision comes first: a batch that goes to the worker needs neither bins nor launch descriptors)
-    {
-        int cur = -1;   // (a thread-local read; hipSetDevice costs a microsecond per launch)
-        if (hipGetDevice(&cur) != hipSuccess || cur != hb->device) HIPCHK(hipSetDevice(hb->device));
-    }
-    // the previous launch of this slot must have drained before its staging buffer is rewritten
-    // (already the case when the host has just harvested the slot's late results)
-    if (S.busy) if (int rcw = hb->wait_slot(S)) return rcw;
-    drain_profile(hb, S);
-    S.busy = true;
-    LP(1);
-    // ---- narrow batch: hand the blankets to the persistent worker instead of launching
-    // While the worker runs nothing else is submitted to the device: HIP multiplexes streams onto a few hardware queues
-    // and a dispatch queued behind the never-ending worker kernel would wait for it. So a batch goes to the worker
-    // whole (every blanket eligible) or the worker is retired first and the batch is launched as before.
-    static const bool worker_env = [] { const char *e = getenv("SPG_WORKER"); return !(e && e[0] == '0'); }();
-    static const bool worker_stamp = [] { const char *e = getenv("SPG_WORKER_STAMP"); return e && e[0] == '1'; }();
-    // (not for the first two batches after a synchronisation: a call that removes a handful of vertices, e.g. online
-    //  decimation, is cheaper as a plain launch than as worker start + stop)
-    hb->batches_in_call++;
-    bool to_worker = worker_env && hb->large_bar && !hb->worker.disabled && rd->mail_len > 0 && o.algorithm == SPG_ALG_NFR && o.topology == SPG_TOPO_TREE &&
-                     o.lin_point == SPG_LIN_GLOBAL && o.flags == 0 && rd->count <= 512 && !hb->force_one_wave &&
-                     hb->worker_cooldown == 0 && (hb->batches_in_call > 2 || hb->worker.running);
-    if (hb->worker_cooldown > 0) hb->worker_cooldown--;
-    if (to_worker) {
-        // eligible: pose-pose edges only, one removed vertex, n <= kWorkerMaxN, packet fits the staging area
-        for (int b = rd->first; b < rd->first + rd->count && to_worker; b++) {
-            const spg_blanket_desc &bd = rd->blankets[b];
-            const int k = bd.n_vert - bd.n_remove;
-            int nev = 0;
-            bool bin = true;
-            for (int e = bd.edge_begin; e < bd.edge_begin + bd.n_edge; e++) { nev += rd->edges[e].nv; bin &= (rd->edges[e].kind == SPG_EDGE_BINARY); }
-            const int words = kPktHdr + bd.n_vert + 3 * bd.n_edge + (nev + 1) / 2;
-            to_worker = bin && bd.n_remove == 1 && k >= 1 && D * k <= kWorkerMaxN && words <= kPktWords && bd.tinfo_off < 0;
-        }
-        if (!to_worker) hb->worker_cooldown = 8;   // mixed batches: stay with launches for a while rather than stop / start per batch
-    }
-    if (to_worker) {
-        const size_t n_push = (size_t)rd->count;
-        int wrc = 0;
-        const size_t need = n_push * (size_t)kPktWords * 8, mneed = (size_t)rd->mail_len * 8;
-        if (need > S.c_pkt || mneed > S.c_mail) {
-            if (int rc2 = hb->worker_stop()) return rc2;   // hipFree waits for the device: nothing may be spinning on it
-            if (need > S.c_pkt) {
-                if (S.d_pkt) { HIPCHK(hipFree(S.d_pkt)); S.d_pkt = nullptr; S.c_pkt = 0; }
-                size_t nc = std::max(need, (size_t)512 * kPktWords * 8);
-                if (hipExtMallocWithFlags(&S.d_pkt, nc, hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); hb->worker.disabled = true; }
-                else S.c_pkt = nc;
-            }
-            if (mneed > S.c_mail) {
-                if (S.h_mail) HIPCHK(hipHostFree(S.h_mail));
-                size_t nc = std::max(mneed, S.c_mail * 2);
-                HIPCHK(hipHostMalloc(&S.h_mail, nc, hipHostMallocMapped));
-                HIPCHK(hipHostGetDevicePointer(&S.d_mail, S.h_mail, 0));
-                memset(S.h_mail, 0, nc);
-                S.c_mail = nc;
-            }
-        }
-        if (!hb->worker.disabled) wrc = hb->worker_start(D, SPG_ALG_NFR);
-        if (wrc < 0) return wrc;
-        if (wrc == 0 && !hb->worker.disabled) {
-            HipBackend::Worker &W = hb->worker;
-            unsigned long long *pbase = (unsigned long long *)S.d_pkt;
-            const double *hmail = (const double *)S.h_mail;
-            S.final_word = SPG_FINAL_WORD(rd->tag);
-            double wbytes = 0;
-            for (size_t i = 0; i < n_push; i++) {
-                const int32_t b = rd->first + (int32_t)i;
-                const spg_blanket_desc &bd = rd->blankets[b];
-                unsigned long long pkt[kPktWords];
-                int nev = 0;
-                for (int e = bd.edge_begin; e < bd.edge_begin + bd.n_edge; e++) nev += rd->edges[e].nv;
-                const int words = kPktHdr + bd.n_vert + 3 * bd.n_edge + (nev + 1) / 2;
-                auto pack = [](int lo, int hi) { return (unsigned long long)(uint32_t)lo | ((unsigned long long)(uint32_t)hi << 32); };
-                pkt[0] = (unsigned long long)(uintptr_t)arena;
-                pkt[1] = (unsigned long long)(uintptr_t)S.d_mail;
-                pkt[2] = (unsigned long long)rd->mail_base;
-                pkt[3] = (unsigned long long)bd.out_off; pkt[4] = (unsigned long long)bd.new_off; pkt[5] = (unsigned long long)bd.tinfo_off;
-                pkt[6] = pack(bd.n_vert, bd.n_remove); pkt[7] = pack(bd.n_edge, bd.n_new_max); pkt[8] = pack(bd.n_new_vert_max, bd.pad_);
-                pkt[9] = pack(o.topology, o.flags); pkt[10] = pack(o.lin_point, rd->tag);
-                memcpy(&pkt[11], &o.chord_ratio, 8);
-                pkt[12] = pack(words, nev | (worker_stamp ? 0x40000000 : 0));
-                int w = kPktHdr;
-                for (int v = 0; v < bd.n_vert; v++) pkt[w++] = (unsigned long long)rd->vert_pose_off[bd.vert_begin + v];
-                int32_t *evp = (int32_t *)(pkt + kPktHdr + bd.n_vert + 3 * bd.n_edge);
-                int evn = 0;
-                double by = 8.0 * ((D == 6) ? 7 : 3) * bd.n_vert + 12.0 + 8.0 * bd.new_len;
-                for (int e = bd.edge_begin; e < bd.edge_begin + bd.n_edge; e++) {
-                    spg_edge_ref er = rd->edges[e];
-                    for (int t = 0; t < er.nv; t++) evp[evn + t] = rd->edge_vert[er.vbegin + t];
-                    er.vbegin = evn;
-                    evn += er.nv;
-                    memcpy(&pkt[w], &er, 24);
-                    w += 3;
-                    by += 4.0 * er.nv + 8.0 * er.len;
-                }
-                if (evn & 1) evp[evn] = 0;
-                wbytes += by;
-                unsigned long long *dst = pbase + i * (size_t)kPktWords;
-                memcpy(dst, pkt, (size_t)words * 8);                       // through the BAR (write-combined)
-                W.q->item[(W.tail + i) % kQCap] = (unsigned long long)(uintptr_t)dst;
-                S.finals.push_back(hmail + (bd.out_off - rd->mail_base) + 5);
-            }
-            bar_fence();
-            W.tail += n_push;
-            for (int c = 0; c < W.bells; c++) W.q->tail[c * kBellStride] = W.tail;   // the doorbells
-            bar_fence();
-            W.last_push = std::chrono::steady_clock::now();
-            W.bytes += wbytes; W.blankets += (long long)n_push;
-            static const bool echo_test = [] { const char *e = getenv("SPG_WORKER_ECHO_TEST"); return e && e[0] == '1'; }();
-            if (echo_test) {
-                // diagnostic: doorbell -> ready word of the batch's first blanket, on the host clock
-                const volatile double *rw = S.finals.front();
-                const double want_r = SPG_READY_WORD(rd->tag), want_f = SPG_FINAL_WORD(rd->tag);
-                auto t0 = std::chrono::steady_clock::now();
-                while (*rw != want_r && *rw != want_f) { if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 1.0) break; }
-                static double acc = 0; static long cnt = 0;
-                acc += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); cnt++;
-                if (cnt % 252 == 0) { fprintf(stderr, "worker echo test: doorbell -> first blanket ready %.1f us (avg over %ld batches of ~%zu)\n", acc / cnt, cnt, n_push); acc = 0; cnt = 0; }
-            }
-            return 0;                                                      // the whole batch is with the worker
-        }
-    }
-    if (int rcw = hb->worker_stop()) return rcw;                           // a launch follows: the worker must not be in its way
-    // ---- bin this rank's blankets by the LDS their tiles need
-    struct Bin { std::vector<int32_t> &list; int kmax = 0, mmax = 0, smax = 0; double bytes = 0; };
-    const int NB = 5;
-    const size_t lim[NB - 1] = {24 * 1024, 40 * 1024, 80 * 1024, (size_t)hb->lds_limit};
-    for (auto &v : S.bin_lists) v.clear();   // per-slot scratch: no allocation per launch
-    Bin bins[NB] = {{S.bin_lists[0]}, {S.bin_lists[1]}, {S.bin_lists[2]}, {S.bin_lists[3]}, {S.bin_lists[4]}};
-    for (int b = rd->first; b < rd->first + rd->count; b++) {
-        const spg_blanket_desc &bd = rd->blankets[b];
-        int k = bd.n_vert - bd.n_remove, m = bd.n_remove;
-        // (binned with the carve-up of the widest team any LDS variant uses, so that no variant outgrows its bin)
-        Layout L = make_layout(D, 256, k, m, o.algorithm, o.topology, bd.pad_);
-        size_t need = (size_t)(L.small_doubles + L.mat_doubles) * 8;
-        int bi = NB - 1;
-        for (int i = 0; i < NB - 1; i++) if (need <= lim[i]) { bi = i; break; }
-        bins[bi].list.push_back(b);
-        if (hb->profiling) {
-            // algorithmic HBM bytes of this blanket: poses + (2 x i32 + record) per edge
-            // + new records + (kld f64 + status i32)
-            const int ps = (D == 6) ? 7 : 3;
-            double by = 8.0 * ps * bd.n_vert + 12.0;
-            for (int e = bd.edge_begin; e < bd.edge_begin + bd.n_edge; e++) by += 4.0 * rd->edges[e].nv + 8.0 * rd->edges[e].len;
-            by += 8.0 * bd.new_len;
-            bins[bi].bytes += by;
-        }
-        bins[bi].kmax = std::max(bins[bi].kmax, k);
-        bins[bi].mmax = std::max(bins[bi].mmax, m);
-        bins[bi].smax = std::max(bins[bi].smax, (int)bd.pad_);
-    }
-    // NFR blankets whose pattern (Dense / Subgraph with more than k-1 edges) has no closed form: interior point, its own
-    // kernel (spg_nfr_ip.hip), one workgroup per blanket after the launches below
-    std::vector<int32_t> ip_list;
-    int ip_closed = 0;
-    int64_t ip_stride = 0, ip_hot = 0;
-    if (o.algorithm == SPG_ALG_NFR) {
-        const bool cliquey = o.topology == SPG_TOPO_CLIQUEY_SUBGRAPH || o.topology == SPG_TOPO_CLIQUEY_DENSE;
-        for (int i = 0; i < NB; i++) {
-            size_t keep = 0;
-            int kmax = 0, mmax = 0, smax = 0;
-            for (int32_t b : bins[i].list) {
-                const spg_blanket_desc &bd = rd->blankets[b];
-                const int k = bd.n_vert - bd.n_remove, m = bd.n_remove;
-                const int E = spg::nfr_ip_pattern_size(o.topology, o.chord_ratio, k);
-                bool has_multi = false;
-                for (int e = bd.edge_begin; e < bd.edge_begin + bd.n_edge; e++) has_multi |= rd->edges[e].kind == SPG_EDGE_MULTI;
-                const bool ip = k >= 3 && !cliquey && E > k - 1;           // uncorrelated pattern without a closed form
-                // correlated patterns (and any blanket that holds a correlated edge) take the same generic kernel's closed form
-                // (clusters under the Local linearisation point too: the blanket kernel's own Local branch is for one removed vertex)
-                const bool local_cluster = o.lin_point != SPG_LIN_GLOBAL && m > 1 && k >= 2;
-                // (and blankets whose Chow-Liu pair tables and side buffers outgrow LDS even with the tiles in the L2 workspace —
-                //  k beyond ~130: until round 3 SPG_ECAPACITY — the generic kernel keeps everything in its workspace, k <= 256)
-                bool too_big = false;
-                if (i == NB - 1 && k >= 2) {
-                    const bool lm_ = o.lin_point != SPG_LIN_GLOBAL;
-                    Layout Lw = make_layout(D, lm_ ? 256 : 1024, k, m, o.algorithm, o.topology, bd.pad_);
-                    too_big = (size_t)Lw.small_doubles * 8 > (size_t)hb->lds_limit;
-                }
-                if (ip || (cliquey && k >= 3) || (has_multi && k >= 2) || local_cluster || too_big) {
-                    const int msub = (int)((1 + o.chord_ratio) * (k - 1));
-                    const bool masks = o.topology == SPG_TOPO_CLIQUEY_SUBGRAPH && msub < k * (k - 1) / 2;   // fillCliques on 64-bit vertex masks
-                    // (interior point: Newton systems up to 2 048 variables in LDS-resident forms, up to spg::kIpMaxVars through the
-                    //  blocked factorisation — one workgroup, 0.1 s per Newton step at 2 400 variables, 1 s at 4 900, 5 s at 8 300)
-                    if ((ip && (int64_t)D * D * E > spg::kIpMaxVars) || (masks && k > 64) || k > 256) {
-                        snprintf(err, sizeof hb->err, "interior-point / correlated NFR: a blanket with k=%d kept vertices and %d new measurements is beyond the generic kernel (Newton systems up to %d variables; k <= 64 for CliqueySubgraph, 256 otherwise)", k, E, spg::kIpMaxVars);
-                        return SPG_ECAPACITY;
-                    }
-                    ip_list.push_back(b);
-                    if (!ip) ip_closed++;        // (closed form: every correlated pattern, trees with correlated input edges)
-                    int64_t hot = 0;
-                    ip_stride = std::max(ip_stride, spg::nfr_ip_workspace(D, k, m, E, ip ? 0 : 1, &hot));
-                    ip_hot = std::max(ip_hot, hot);
-                    continue;
-                }
-                bins[i].list[keep++] = b;
-                kmax = std::max(kmax, k); mmax = std::max(mmax, m); smax = std::max(smax, (int)bd.pad_);
-            }
-            if (keep != bins[i].list.size()) { bins[i].list.resize(keep); bins[i].kmax = kmax; bins[i].mmax = mmax; bins[i].smax = smax; }
-        }
-    }
-    // Blankets whose side buffers (Chow-Liu pair tables, GLC batch buffers) exceed LDS even with the tiles in the L2
-    // workspace: GLC Dense ones go through the dense HBM pipeline on the matrix cores (spg_dense.hip) after the
-    // launches below, one at a time; for the others there is no path (SPG_ECAPACITY, as before).
-    std::vector<int32_t> big_list;
-    static const bool force_big = [] { const char *e = getenv("SPG_FORCE_BIG"); return e && e[0] == '1'; }();   // diagnostic / tests
-    if (force_big && o.algorithm == SPG_ALG_GLC && o.topology == SPG_TOPO_DENSE && o.lin_point == SPG_LIN_GLOBAL) {
-        // every blanket with at least one kept vertex takes the dense pipeline (parity of that path on small blankets)
-        for (int i = 0; i < NB; i++) {
-            size_t keep = 0;
-            for (int32_t b : bins[i].list) {
-                if (rd->blankets[b].n_vert - rd->blankets[b].n_remove >= 2 && rd->blankets[b].n_edge > 0) big_list.push_back(b);
-                else bins[i].list[keep++] = b;
-            }
-            bins[i].list.resize(keep);
-        }
-        std::sort(big_list.begin(), big_list.end());
-    } else {
-        Bin &bb = bins[NB - 1];
-        size_t keep = 0;
-        int kmax = 0, mmax = 0, smax = 0;
-        for (int32_t b : bb.list) {
-            const spg_blanket_desc &bd = rd->blankets[b];
-            const int k = bd.n_vert - bd.n_remove, m = bd.n_remove;
-            Layout Lb = make_layout(D, 256, k, m, o.algorithm, o.topology, bd.pad_);
-            if ((size_t)Lb.small_doubles * 8 <= (size_t)hb->lds_limit) {
-                bb.list[keep++] = b;
-                kmax = std::max(kmax, k); mmax = std::max(mmax, m); smax = std::max(smax, (int)bd.pad_);
-                continue;
-            }
-            if (!(o.algorithm == SPG_ALG_GLC && o.topology == SPG_TOPO_DENSE && o.lin_point == SPG_LIN_GLOBAL)) {
-                snprintf(err, sizeof hb->err, "blanket too large for LDS side buffers: k=%d m=%d (only GLC Dense blankets have a large-blanket path)", k, m);
-                return SPG_ECAPACITY;
-            }
-            big_list.push_back(b);
-        }
-        if (!big_list.empty()) { bb.list.resize(keep); bb.kmax = kmax; bb.mmax = mmax; bb.smax = smax; }
-    }
-    LP(0);
-    // ---- upload the round's descriptors (one pinned staging buffer, async copies)
-    size_t s_blk = sizeof(spg_blanket_desc) * (size_t)rd->n_blankets;
-    size_t s_vpo = sizeof(int64_t) * (size_t)rd->n_vert_total;
-    size_t s_er = sizeof(spg_edge_ref) * (size_t)rd->n_edge_total;
-    size_t s_ev = sizeof(int32_t) * (size_t)rd->n_edge_vert_total;
-    size_t s_list = sizeof(int32_t) * (size_t)rd->count;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o_blk = 0, o_vpo = o_blk + al(s_blk), o_er = o_vpo + al(s_vpo), o_ev = o_er + al(s_er), o_list = o_ev + al(s_ev);
-    size_t tot = o_list + al(s_list);
-    // Where the descriptors of this launch go:
-    //  - small launch, large-BAR system: the host stores them straight into (fine-grained) device memory —
-    //    posted writes ahead of the doorbell, no copy engine hop, and the kernel reads local HBM;
-    //  - small launch otherwise: the kernel reads them from the mapped pinned staging buffer over PCIe;
-    //  - large launch: one host->device copy from the staging buffer.
-    static const int mapped_limit = [] { const char *e = getenv("SPG_MAPPED_DESC"); return e ? atoi(e) : 512; }();
-    static const bool bar_ok = [] { const char *e = getenv("SPG_BAR_DESC"); return !(e && e[0] == '0'); }();
-    const bool small = (long long)rd->count <= (long long)mapped_limit;
-    bool via_bar = small && hb->large_bar && bar_ok;
-    char *st;
-    if (via_bar && tot > S.c_bar) {
-        if (S.d_bar) { if (int rc = hb->worker_stop()) return rc; HIPCHK(hipFree(S.d_bar)); S.d_bar = nullptr; S.c_bar = 0; }
-        size_t nc = std::max(tot, (size_t)1 << 16);
-        if (hipExtMallocWithFlags(&S.d_bar, nc, hipDeviceMallocFinegrained) == hipSuccess) S.c_bar = nc;
-        else { (void)hipGetLastError(); S.d_bar = nullptr; hb->large_bar = false; via_bar = false; }   // fall back to the mapped staging buffer
-    }
-    if (via_bar) {
-        st = (char *)S.d_bar;   // write-only from the host
-    } else {
-        if (int rc = hb->ensure_stage(S, tot)) return rc;
-        if (!small) if (int rc = hb->ensure(S, &S.d_desc, &S.c_desc, tot)) return rc;
-        st = (char *)S.h_stage;
-    }
-    memcpy(st + o_blk, rd->blankets, s_blk);
-    memcpy(st + o_vpo, rd->vert_pose_off, s_vpo);
-    memcpy(st + o_er, rd->edges, s_er);
-    if (s_ev) memcpy(st + o_ev, rd->edge_vert, s_ev);
-    {
-        int32_t *lst = (int32_t *)(st + o_list);
-        size_t p = 0;
-        for (int i = 0; i < NB; i++) for (int32_t b : bins[i].list) lst[p++] = b;
-        for (int32_t b : ip_list) lst[p++] = b;      // (the lists together never exceed rd->count entries)
-    }
-    char *desc_base;
-    if (via_bar) {
-        std::atomic_thread_fence(std::memory_order_release);
-#if defined(__x86_64__)
-        __builtin_ia32_sfence();   // write-combining buffers drained before the launch rings the doorbell
-#endif
-        desc_base = (char *)S.d_bar;
-    } else if (small) {
-        desc_base = (char *)S.d_stage;
-    } else {
-        desc_base = (char *)S.d_desc;
-        HIPCHK(hipMemcpyAsync(S.d_desc, st, tot, hipMemcpyHostToDevice, S.stream));
-    }
-    LP(2);
-    double *mail_dev = nullptr;
-    if (rd->mail_len > 0) {
-        size_t need = (size_t)rd->mail_len * 8;
-        if (need > S.c_mail) {
-            if (int rc = hb->worker_stop()) return rc;
-            if (S.h_mail) HIPCHK(hipHostFree(S.h_mail));
-            size_t nc = std::max(need, S.c_mail * 2);
-            HIPCHK(hipHostMalloc(&S.h_mail, nc, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(&S.d_mail, S.h_mail, 0));
-            memset(S.h_mail, 0, nc);   // a fresh mailbox never looks ready
-            S.c_mail = nc;
-        }
-        mail_dev = (double *)S.d_mail;
-    }
-    // ---- launch each non-empty bin
-    KArgs ka;
-    ka.arena = (double *)arena;
-    ka.blk = (const spg_blanket_desc *)(desc_base + o_blk);
-    ka.vpo = (const int64_t *)(desc_base + o_vpo);
-    ka.er = (const spg_edge_ref *)(desc_base + o_er);
-    ka.ev = (const int32_t *)(desc_base + o_ev);
-    ka.mail = mail_dev;
-    ka.mail_base = rd->mail_base;
-    ka.gws = nullptr; ka.gws_stride = 0;
-    ka.topology = o.topology; ka.algorithm = o.algorithm; ka.flags = o.flags; ka.chord_ratio = o.chord_ratio; ka.lin_point = o.lin_point; ka.tag = rd->tag;
-    // Local linearisation point: the kernel variant that carries the blanket-level LM
-    const bool lm = (o.algorithm == SPG_ALG_NFR) && (o.lin_point != SPG_LIN_GLOBAL);
-    size_t list_off = 0;
-    for (int i = 0; i < NB; i++) {
-        int nb = (int)bins[i].list.size();
-        if (nb == 0) continue;
-        ka.list = (const int32_t *)(desc_base + o_list) + list_off;
-        list_off += nb;
-        int rc;
-        if (i < NB - 1) {
-            Layout L = make_layout(D, 64, bins[i].kmax, bins[i].mmax, o.algorithm, o.topology, bins[i].smax);
-            size_t lds = (size_t)(L.small_doubles + L.mat_doubles) * 8;
-            // the (kmax, mmax, smax) envelope can exceed the device limit although every member fits
-            // (each needs <= lim[i] <= lds_limit): clamp, the per-block carve-up uses its own k, m
-            if (lds > (size_t)hb->lds_limit) lds = (size_t)hb->lds_limit;
-            // latency mode: a launch that cannot fill the chip (<= 2 blankets per CU) gives every blanket
-            // two wavefronts so the Chow-Liu and gauge chains overlap; throughput mode keeps one
-            const bool two_waves = (o.algorithm == SPG_ALG_NFR) && nb <= 512 && D * bins[i].kmax <= kWaveMax && !hb->force_one_wave;
-            if (two_waves) {
-                Layout L2 = make_layout(D, 128, bins[i].kmax, bins[i].mmax, o.algorithm, o.topology, bins[i].smax);
-                size_t lds2 = std::min((size_t)(L2.small_doubles + L2.mat_doubles) * 8, (size_t)hb->lds_limit);
-                if (lm) rc = (D == 6) ? launch_bin<6, 128, false, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds2, bins[i].bytes) : launch_bin<3, 128, false, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds2, bins[i].bytes);
-                else rc = (D == 6) ? launch_bin<6, 128, false, SPG_ALG_NFR>(hb, S, ka, nb, lds2, bins[i].bytes) : launch_bin<3, 128, false, SPG_ALG_NFR>(hb, S, ka, nb, lds2, bins[i].bytes);
-            } else if ((o.algorithm == SPG_ALG_NFR) && !lm && nb <= 1024 && D * bins[i].kmax > kWaveMax && !hb->force_one_wave) {
-                // tiles beyond the register-resident size (n > 24) run the LDS-cooperative routines: their O(n^2) inner
-                // steps want lanes, and a launch this small leaves the chip empty anyway — four wavefronts per blanket
-                // (parking.g2o: 0.70 -> ms per launch of such blankets)
-                Layout L4 = make_layout(D, 256, bins[i].kmax, bins[i].mmax, o.algorithm, o.topology, bins[i].smax);
-                size_t lds4 = std::min((size_t)(L4.small_doubles + L4.mat_doubles) * 8, (size_t)hb->lds_limit);
-                rc = (D == 6) ? launch_bin<6, 256, false, SPG_ALG_NFR>(hb, S, ka, nb, lds4, bins[i].bytes) : launch_bin<3, 256, false, SPG_ALG_NFR>(hb, S, ka, nb, lds4, bins[i].bytes);
-            } else if (o.algorithm == SPG_ALG_GLC)
-                rc = (D == 6) ? launch_bin<6, 64, false, SPG_ALG_GLC>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 64, false, SPG_ALG_GLC>(hb, S, ka, nb, lds, bins[i].bytes);
-            else if (lm)
-                rc = (D == 6) ? launch_bin<6, 64, false, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 64, false, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds, bins[i].bytes);
-            else
-                rc = (D == 6) ? launch_bin<6, 64, false, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 64, false, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes);
-        } else {
-            // NFR: eight wavefronts per blanket — the tiles sit in L2, every step of the cooperative routines is a round of
-            // ~1 us accesses, and only lanes hide that (parking.g2o: 3.1 -> ms per launch of such blankets)
-            const bool wide = (o.algorithm == SPG_ALG_NFR) && !lm && !hb->force_one_wave;
-            const int ntg = wide ? 1024 : 256;
-            Layout L = make_layout(D, ntg, bins[i].kmax, bins[i].mmax, o.algorithm, o.topology, bins[i].smax);
-            size_t lds = (size_t)L.small_doubles * 8;
-            if (lds > (size_t)hb->lds_limit) { snprintf(err, sizeof hb->err, "blanket too large for LDS side buffers: k=%d m=%d", bins[i].kmax, bins[i].mmax); return SPG_ECAPACITY; }
-            size_t stride = ((size_t)L.mat_doubles + 31) & ~(size_t)31;
-            if (int rc2 = hb->ensure(S, &S.d_gws, &S.c_gws, stride * 8 * (size_t)nb)) return rc2;
-            ka.gws = (double *)S.d_gws;
-            ka.gws_stride = (int64_t)stride;
-            if (o.algorithm == SPG_ALG_GLC)
-                rc = (D == 6) ? launch_bin<6, 256, true, SPG_ALG_GLC>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 256, true, SPG_ALG_GLC>(hb, S, ka, nb, lds, bins[i].bytes);
-            else if (lm)
-                rc = (D == 6) ? launch_bin<6, 256, true, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 256, true, SPG_ALG_NFR_LM>(hb, S, ka, nb, lds, bins[i].bytes);
-            else if (wide)
-                rc = (D == 6) ? launch_bin<6, 1024, true, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 1024, true, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes);
-            else
-                rc = (D == 6) ? launch_bin<6, 256, true, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes) : launch_bin<3, 256, true, SPG_ALG_NFR>(hb, S, ka, nb, lds, bins[i].bytes);
-        }
-        if (rc) return rc;
-    }
-    // ---- interior-point NFR blankets
-    if (!ip_list.empty()) {
-        if (int rc2 = hb->ensure(S, &S.d_ipws, &S.c_ipws, (size_t)ip_stride * 8 * ip_list.size())) return rc2;
-        // The workspace is reused from launch to launch and from graph to graph: cleared, so that what a blanket finds in its
-        // slice never depends on what ran before it in the process (a run of several graphs through one context died with a
-        // core dump in round 2 where each graph on its own passes; hipMalloc'ed memory is not zeroed either).
-        HIPCHK(hipMemsetAsync(S.d_ipws, 0, (size_t)ip_stride * 8 * ip_list.size(), S.stream));
-        spg::IpArgs ia{};
-        ia.arena = (double *)arena; ia.blk = ka.blk; ia.vpo = ka.vpo; ia.er = ka.er; ia.ev = ka.ev;
-        ia.list = (const int32_t *)(desc_base + o_list) + list_off;
-        ia.ws = (double *)S.d_ipws; ia.ws_stride = ip_stride; ia.mail = mail_dev; ia.mail_base = rd->mail_base;
-        ia.topology = o.topology; ia.lin_point = o.lin_point; ia.tag = rd->tag; ia.chord_ratio = o.chord_ratio;
-        if (o.lin_point != SPG_LIN_GLOBAL) {
-            // ---- Local linearisation point for these blankets (pre-pass, see local_point_kernel): scratch poses, closed-form
-            // re-initialisation on the device, else the reference's 10 LM iterations with the first removed vertex fixed —
-            // the dense LM of optimize() on the blanket as a small graph, host-driven, one blanket after the other — and a
-            // second table of pose offsets that points the generic kernel at the scratch blocks.
-            const int PSl = (D == 6) ? 7 : 3;
-            const size_t nl = ip_list.size();
-            std::vector<int64_t> lp_off(nl);
-            int64_t lp_tot = 0;
-            for (size_t i = 0; i < nl; i++) { lp_off[i] = lp_tot; lp_tot += (int64_t)rd->blankets[ip_list[i]].n_vert * PSl; }
-            const size_t meta_bytes = nl * 8 + nl * 4 + (size_t)rd->n_vert_total * 8 + 64;
-            if (int rc2 = hb->ensure(S, &S.d_lpose, &S.c_lpose, (size_t)lp_tot * 8 + 64)) return rc2;
-            if (int rc2 = hb->ensure(S, &S.d_lmeta, &S.c_lmeta, meta_bytes)) return rc2;
-            int64_t *d_lp_off = (int64_t *)S.d_lmeta, *d_vpo2 = d_lp_off + nl;
-            int32_t *d_flag = (int32_t *)(d_vpo2 + rd->n_vert_total);
-            const int64_t scratch0 = ((intptr_t)S.d_lpose - (intptr_t)arena) / 8;   // the scratch block as an "arena offset"
-            std::vector<int64_t> vpo2(rd->vert_pose_off, rd->vert_pose_off + rd->n_vert_total);
-            for (size_t i = 0; i < nl; i++) {
-                const spg_blanket_desc &bd = rd->blankets[ip_list[i]];
-                for (int v = 0; v < bd.n_vert; v++) vpo2[(size_t)bd.vert_begin + v] = scratch0 + lp_off[i] + (int64_t)v * PSl;
-            }
-            HIPCHK(hipMemcpyAsync(d_lp_off, lp_off.data(), nl * 8, hipMemcpyHostToDevice, S.stream));
-            HIPCHK(hipMemcpyAsync(d_vpo2, vpo2.data(), (size_t)rd->n_vert_total * 8, hipMemcpyHostToDevice, S.stream));
-            if (D == 6) hipLaunchKernelGGL((local_point_kernel<6>), dim3((unsigned)nl), dim3(64), 0, S.stream, (const double *)arena, (double *)S.d_lpose, ka.blk, ka.vpo, ka.er, ka.ev, ia.list, (const int64_t *)d_lp_off, d_flag);
-            else hipLaunchKernelGGL((local_point_kernel<3>), dim3((unsigned)nl), dim3(64), 0, S.stream, (const double *)arena, (double *)S.d_lpose, ka.blk, ka.vpo, ka.er, ka.ev, ia.list, (const int64_t *)d_lp_off, d_flag);
-            HIPCHK(hipGetLastError());
-            std::vector<int32_t> h_flag(nl);
-            HIPCHK(hipMemcpyAsync(h_flag.data(), d_flag, nl * 4, hipMemcpyDeviceToHost, S.stream));
-            HIPCHK(hipStreamSynchronize(S.stream));
-            for (size_t i = 0; i < nl; i++) {
-                if (h_flag[i]) continue;
-                const spg_blanket_desc &bd = rd->blankets[ip_list[i]];
-                // the blanket as a small graph (local vertex = blanket-local index), vertex 0 fixed
-                std::vector<int32_t> pos(bd.n_vert), rowptr(bd.n_vert + 1, 0), inc;
-                std::vector<int64_t> lvpo(bd.n_vert);
-                for (int l = 0; l < bd.n_vert; l++) { pos[l] = l == 0 ? -1 : (l - 1) * D; lvpo[l] = scratch0 + lp_off[i] + (int64_t)l * PSl; }
-                std::vector<std::vector<int32_t>> per(bd.n_vert);
-                for (int e = 0; e < bd.n_edge; e++) {
-                    const spg_edge_ref &r = rd->edges[bd.edge_begin + e];
-                    for (int t = 0; t < r.nv; t++) {
-                        const int32_t l = rd->edge_vert[r.vbegin + t];
-                        if (per[l].empty() || per[l].back() != e) per[l].push_back(e);
-                    }
-                }
-                for (int l = 0; l < bd.n_vert; l++) { inc.insert(inc.end(), per[l].begin(), per[l].end()); rowptr[l + 1] = (int32_t)inc.size(); }
-                spg::DenseGraphIn in;
-                in.D = D; in.nv = bd.n_vert; in.ne = bd.n_edge;
-                in.pos = pos.data(); in.vpo = lvpo.data(); in.rowptr = rowptr.data(); in.inc = inc.data();
-                in.er = rd->edges + bd.edge_begin; in.ev = rd->edge_vert; in.n_ev = rd->n_edge_vert_total; in.dev_arena = arena;
-                spg_optimize_stats lm_stats{};
-                if (int lrc = spg::hip_dense_optimize((void *)S.stream, in, D * (bd.n_vert - 1), 10, lm_stats, hb->err, sizeof hb->err)) return lrc;
-            }
-            ia.vpo = (const int64_t *)d_vpo2;
-            ia.lin_point = SPG_LIN_GLOBAL;   // the scratch poses ARE the local linearisation point: taken as they are
-        }
-        if (int rc2 = spg::hip_nfr_ip_launch((void *)S.stream, D, ia, (int)ip_list.size(), ip_closed, ip_hot)) { snprintf(err, sizeof hb->err, "launch of the interior-point kernel failed"); return rc2; }
-        // (this kernel comes AFTER the event a bin launch left in wait_ev: waiting for the slot must mean the whole stream.
-        //  Until round 3 wait_slot returned when the bin kernel was done — with a cluster of 150 vertices still running in
-        //  this one, the commit read whatever the mailbox held at its record's place: silently wrong graphs on parking.g2o
-        //  under CliqueyDense, and a segmentation fault when the stale words were not zeros.)
-        S.wait_ev = nullptr;
-        S.stream_dirty = true;
-        S.busy = true;
-    }
-    // ---- large GLC Dense blankets: dense in HBM, O(n^3) parts on the fp64 matrix cores
-    for (int32_t b : big_list) {
-        const spg_blanket_desc &bd = rd->blankets[b];
-        const int k = bd.n_vert - bd.n_remove, m = bd.n_remove;
-        // the blanket as a local graph: vertices = blanket-local indices (removed first), edges as staged for the kernel
-        const int nm = D * m, Nm = (nm + 63) / 64 * 64;
-        std::vector<int32_t> pos(bd.n_vert), rowptr(bd.n_vert + 1, 0), inc;
-        for (int l = 0; l < bd.n_vert; l++) pos[l] = l < m ? l * D : Nm + (l - m) * D;
-        std::vector<std::vector<int32_t>> per(bd.n_vert);
-        for (int e = 0; e < bd.n_edge; e++) {
-            const spg_edge_ref &er = rd->edges[bd.edge_begin + e];
-            for (int t = 0; t < er.nv; t++) {
-                int32_t l = rd->edge_vert[er.vbegin + t];
-                if (per[l].empty() || per[l].back() != e) per[l].push_back(e);
-            }
-        }
-        for (int l = 0; l < bd.n_vert; l++) { inc.insert(inc.end(), per[l].begin(), per[l].end()); rowptr[l + 1] = (int32_t)inc.size(); }
-        spg::DenseGraphIn in;
-        in.D = D; in.nv = bd.n_vert; in.ne = bd.n_edge;
-        in.pos = pos.data(); in.vpo = rd->vert_pose_off + bd.vert_begin; in.rowptr = rowptr.data(); in.inc = inc.data();
-        in.er = rd->edges + bd.edge_begin; in.ev = rd->edge_vert; in.n_ev = rd->n_edge_vert_total; in.dev_arena = arena;
-        double *orec = mail_dev ? (mail_dev + (bd.out_off - rd->mail_base)) : ((double *)arena + bd.out_off);
-        double secs = 0, flops = 0;
-        int brc = spg::hip_big_glc_dense((void *)S.stream, in, m, k, Nm, bd.new_off, orec, bd.n_new_max, rd->tag, &secs, &flops, hb->err, sizeof hb->err);
-        if (brc) return brc;
-        hb->prof_big_ms += 1e3 * secs; hb->prof_big_flops += flops; hb->prof_big_count++;
-        hb->prof_big_nmax = std::max(hb->prof_big_nmax, D * (k + m));
-        S.wait_ev = nullptr;   // (as above: the slot is done when the stream is)
-        S.stream_dirty = true;
-    }
-    LP(3);
-#ifdef SPG_LAUNCH_PROF
-    if (lp_n % 1005 == 0) fprintf(stderr, "launch prof: bins %.2f sync+drain %.2f desc write %.2f launch %.2f us (avg over %ld)\n",
-                                  lp_t[0] / lp_n, lp_t[1] / lp_n, lp_t[2] / lp_n, lp_t[3] / lp_n, lp_n);
-#endif
-    return 0;
-}
-
-static void *hip_alloc(void *user, int64_t doubles) {
-    HipBackend *hb = (HipBackend *)user;
-    void *p = nullptr;
-    if (hipSetDevice(hb->device) != hipSuccess) return nullptr;
-    if (hipMalloc(&p, (size_t)doubles * 8) != hipSuccess) return nullptr;
-    return p;
-}
-static void hip_release(void *user, void *p) {
-    HipBackend *hb = (HipBackend *)user;
-    (void)hb->worker_stop();   // hipFree waits for the whole device
-    (void)hipStreamSynchronize(hb->slots[0].stream);
-    (void)hipFree(p);
-}
-static int hip_upload(void *user, void *dst, const double *src, int64_t doubles) {
-    HipBackend *hb = (HipBackend *)user;
-    char *err = hb->err;
-    if (int rcw = hb->worker_stop()) return rcw;
-    HIPCHK(hipMemcpyAsync(dst, src, (size_t)doubles * 8, hipMemcpyHostToDevice, hb->slots[0].stream));
-    HIPCHK(hipStreamSynchronize(hb->slots[0].stream));
-    return 0;
-}
-static int hip_download(void *user, double *dst, const void *src, int64_t doubles) {
-    HipBackend *hb = (HipBackend *)user;
-    char *err = hb->err;
-    if (int rcw = hb->worker_stop()) return rcw;
-    HIPCHK(hipMemcpyAsync(dst, src, (size_t)doubles * 8, hipMemcpyDeviceToHost, hb->slots[0].stream));
-    HIPCHK(hipStreamSynchronize(hb->slots[0].stream));
-    return 0;
-}
-static int hip_sync(void *user) {
-    HipBackend *hb = (HipBackend *)user;
-    char *err = hb->err;
-    for (auto &S : hb->slots) {
-        if (S.busy || S.wait_ev || !S.finals.empty()) { if (int rcw = hb->wait_slot(S)) return rcw; }
-        else HIPCHK(hipStreamSynchronize(S.stream));   // copies issued outside hip_run_round
-        drain_profile(hb, S);
-    }
-    // a full synchronisation leaves the device idle: the persistent worker retires (it restarts on demand)
-    hb->batches_in_call = 0;
-    return hb->worker_stop();
-}
-static int hip_sync_slot(void *user, int slot) {
-    HipBackend *hb = (HipBackend *)user;
-    char *err = hb->err;
-    HipBackend::Slot &S = hb->slots[slot & (HipBackend::NSLOT - 1)];
-    if (int rcw = hb->wait_slot(S)) return rcw;
-    drain_profile(hb, S);
-    return 0;
-}
-
-static const double *hip_mailbox(void *user) { return (const double *)((HipBackend *)user)->slots[0].h_mail; }
-static const double *hip_mailbox_slot(void *user, int slot) { return (const double *)((HipBackend *)user)->slots[slot & (HipBackend::NSLOT - 1)].h_mail; }
-
-int hip_backend_create(int device, spg_backend *out, char *errbuf, size_t errlen) {
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        snprintf(errbuf, errlen, "no HIP device available (count=%d, requested=%d): %s — libspg_hip has no CPU fallback",
-                 ndev, device, e == hipSuccess ? "ok" : hipGetErrorString(e));
-        return SPG_ENODEV;
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { snprintf(errbuf, errlen, "hipGetDeviceProperties failed"); return SPG_ENODEV; }
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        snprintf(errbuf, errlen, "device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return SPG_ENODEV;
-    }
-    HipBackend *hb = new HipBackend;
-    hb->device = device;
-    bool okc = hipSetDevice(device) == hipSuccess;
-    for (auto &S : hb->slots) okc = okc && hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) == hipSuccess &&
-                                          hipEventCreateWithFlags(&S.done, hipEventDisableTiming) == hipSuccess;
-    if (!okc) {
-        snprintf(errbuf, errlen, "cannot create HIP stream on device %d", device);
-        delete hb;
-        return SPG_EHIP;
-    }
-    { const char *e1 = getenv("SPG_ONE_WAVE"); hb->force_one_wave = e1 && e1[0] == '1'; }
-    hb->lds_limit = (int)prop.sharedMemPerBlock > 0 ? (int)std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024) : 64 * 1024;
-    {
-        int lb = 0;
-        hb->large_bar = hipDeviceGetAttribute(&lb, hipDeviceAttributeIsLargeBar, device) == hipSuccess && lb != 0;
-    }
-    out->user = hb;
-    out->alloc = hip_alloc;
-    out->release = hip_release;
-    out->upload = hip_upload;
-    out->download = hip_download;
-    out->run_round = hip_run_round;
-    out->synchronize = hip_sync;
-    out->mailbox = hip_mailbox;
-    out->synchronize_slot = hip_sync_slot;
-    out->mailbox_slot = hip_mailbox_slot;
-    return 0;
-}
-
-void hip_backend_destroy(spg_backend *b) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return;
-    (void)hipSetDevice(hb->device);
-    (void)hb->worker_stop();
-    if (hb->worker.q) (void)hipFree(hb->worker.q);
-    if (hb->worker.ticket) (void)hipFree(hb->worker.ticket);
-    if (hb->worker.ev_a) (void)hipEventDestroy(hb->worker.ev_a);
-    if (hb->worker.ev_b) (void)hipEventDestroy(hb->worker.ev_b);
-    if (hb->worker.stream) (void)hipStreamDestroy(hb->worker.stream);
-    if (hb->st_pkt) (void)hipFree(hb->st_pkt);
-    if (hb->st_hmail) (void)hipHostFree(hb->st_hmail);
-    for (auto &S : hb->slots) {
-        if (S.d_pkt) (void)hipFree(S.d_pkt);
-        (void)hipStreamSynchronize(S.stream);
-        if (S.d_desc) (void)hipFree(S.d_desc);
-        if (S.d_gws) (void)hipFree(S.d_gws);
-        if (S.d_lpose) (void)hipFree(S.d_lpose);
-        if (S.d_lmeta) (void)hipFree(S.d_lmeta);
-        if (S.h_mail) (void)hipHostFree(S.h_mail);
-        if (S.h_stage) (void)hipHostFree(S.h_stage);
-        if (S.d_bar) (void)hipFree(S.d_bar);
-        if (S.done) (void)hipEventDestroy(S.done);
-        for (auto &t : S.pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-        for (auto &pr : S.pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-        (void)hipStreamDestroy(S.stream);
-    }
-    spg::hip_big_release_scratch();
-    delete hb;
-    b->user = nullptr;
-}
-
-void *hip_backend_stream(spg_backend *b) { return b->user ? (void *)((HipBackend *)b->user)->slots[0].stream : nullptr; }
-const char *hip_backend_error(spg_backend *b) { return b->user ? ((HipBackend *)b->user)->err : ""; }
-int hip_backend_device(spg_backend *b) { return b->user ? ((HipBackend *)b->user)->device : -1; }
-int hip_backend_launches(spg_backend *b) { return b->user ? ((HipBackend *)b->user)->n_launches.load() : 0; }
-void hip_backend_profile(spg_backend *b, int enable) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return;
-    hb->profiling = enable != 0;
-    hb->prof_stride = enable > 1 ? enable : 1;   // enable = n > 1: HIP events around every n-th launch only
-    hb->prof_tick = 0;
-    for (auto &S : hb->slots) { S.prof_ms = S.prof_bytes = 0; S.prof_launches = S.prof_blankets = 0; }
-    hb->prof_worker_ms = hb->prof_worker_bytes = 0; hb->prof_worker_runs = hb->prof_worker_blankets = 0;
-    hb->prof_big_ms = hb->prof_big_flops = 0; hb->prof_big_count = 0; hb->prof_big_nmax = 0;
-}
-void hip_backend_profile_read_worker(spg_backend *b, double *ms, double *bytes, long long *runs, long long *blankets) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return;
-    *ms = hb->prof_worker_ms; *bytes = hb->prof_worker_bytes; *runs = hb->prof_worker_runs; *blankets = hb->prof_worker_blankets;
-}
-void hip_backend_profile_read_big(spg_backend *b, double *ms, double *flops, long long *count, int *nmax) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return;
-    *ms = hb->prof_big_ms; *flops = hb->prof_big_flops; *count = hb->prof_big_count; *nmax = hb->prof_big_nmax;
-}
-int hip_stream_open(spg_backend *b, int D, int slots, int mail_stride, StreamPort *out) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb || !out || slots < 1 || slots > kQCap / 2 || (D != 3 && D != 6)) return SPG_EINVAL;
-    char *err = hb->err;
-    static const bool worker_env = [] { const char *e = getenv("SPG_WORKER"); return !(e && e[0] == '0'); }();
-    if (!worker_env || !hb->large_bar || hb->worker.disabled || hb->force_one_wave) return 1;
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != hb->device) HIPCHK(hipSetDevice(hb->device));
-    }
-    // nothing of an earlier batch may still be running on the launch slots (their kernels would queue behind the worker)
-    for (auto &S : hb->slots) if (S.busy || S.wait_ev || !S.finals.empty()) { if (int rcw = hb->wait_slot(S)) return rcw; drain_profile(hb, S); }
-    const size_t need_pkt = (size_t)slots * kPktWords * 8, need_mail = (size_t)slots * (size_t)mail_stride * 8;
-    if (need_pkt > hb->c_st_pkt || need_mail > hb->c_st_mail) {
-        if (int rc2 = hb->worker_stop()) return rc2;   // hipFree waits for the device: nothing may be spinning on it
-        if (need_pkt > hb->c_st_pkt) {
-            if (hb->st_pkt) { HIPCHK(hipFree(hb->st_pkt)); hb->st_pkt = nullptr; hb->c_st_pkt = 0; }
-            if (hipExtMallocWithFlags(&hb->st_pkt, need_pkt, hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); hb->st_pkt = nullptr; return 1; }
-            hb->c_st_pkt = need_pkt;
-        }
-        if (need_mail > hb->c_st_mail) {
-            if (hb->st_hmail) { HIPCHK(hipHostFree(hb->st_hmail)); hb->st_hmail = nullptr; hb->c_st_mail = 0; }
-            HIPCHK(hipHostMalloc(&hb->st_hmail, need_mail, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(&hb->st_dmail, hb->st_hmail, 0));
-            memset(hb->st_hmail, 0, need_mail);   // a fresh mailbox never looks ready
-            hb->c_st_mail = need_mail;
-        }
-    }
-    int wrc = hb->worker_start(D, SPG_ALG_NFR);
-    if (wrc) return wrc;
-    if (hb->worker.disabled) return 1;
-    hb->batches_in_call += 3;   // (batches that follow in this call may go to the running worker right away)
-    out->pkt = (unsigned long long *)hb->st_pkt;
-    out->q = hb->worker.q;
-    out->tail = hb->worker.tail;
-    out->bells = hb->worker.bells;
-    out->h_mail = (const double *)hb->st_hmail;
-    out->d_mail = (unsigned long long)(uintptr_t)hb->st_dmail;
-    out->mail_stride = mail_stride;
-    out->slots = slots;
-    return 0;
-}
-
-void hip_stream_close(spg_backend *b, const StreamPort *port, double alg_bytes, long long blankets) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb || !port) return;
-    hb->worker.tail = port->tail;
-    hb->worker.bytes += alg_bytes;
-    hb->worker.blankets += blankets;
-    hb->worker.last_push = std::chrono::steady_clock::now();
-}
-
-int hip_backend_end_of_call(spg_backend *b) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return 0;
-    hb->batches_in_call = 0;
-    return hb->worker_stop();
-}
-void hip_backend_profile_read(spg_backend *b, double *ms, double *bytes, long long *launches, long long *blankets) {
-    HipBackend *hb = (HipBackend *)b->user;
-    if (!hb) return;
-    *ms = *bytes = 0; *launches = *blankets = 0;
-    for (auto &S : hb->slots) { *ms += S.prof_ms; *bytes += S.prof_bytes; *launches += S.prof_launches; *blankets += S.prof_blankets; }
 }
 
 }  // namespace spg
