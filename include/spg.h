@@ -62,9 +62,13 @@ enum {
 enum {
     SPG_INFO_RANK_DEFICIENT = 1, /* smalleigs > dim: chooseDimensions path taken (src/logdet_function.cpp:42-59) */
     SPG_INFO_GLC_ROOT_EDGE = 2,  /* a unary GLC root edge survived the 1e-8 cut (src/topology_provider_glc.cpp:134-140) */
-    SPG_INFO_IP_HESSIAN_NOT_PD = 4 /* interior point: a Newton system was not positive definite and that barrier step was given up
+    SPG_INFO_IP_HESSIAN_NOT_PD = 4, /* interior point: a Newton system was not positive definite and that barrier step was given up
                                     (src/pqn/pqn_optimizer.cpp:48-53 solves with the failed LLT unchecked; the loop over rho,
                                     src/optimizer.cpp:60-75, goes on from the same x either way) */
+    SPG_INFO_GLC_KLD_SKIPPED = 8 /* SPG_FLAG_GLC_KLD was set, but the per-blanket KLD of this GLC blanket is not defined by the
+                                    gauge route and stays NaN: trace(C^-1) >= 5e4 (the NFR route's guard), the tail cut an
+                                    eigenvalue of the target (the edges carry fewer than n - d rows), a root edge was emitted, a
+                                    Cholesky factorisation failed, or the blanket took the large-blanket pipeline */
 };
 
 enum {
@@ -85,8 +89,17 @@ typedef struct {
 } spg_options;
 enum {
     SPG_FLAG_RESERVED0 = 1, /* bit 0 is reserved (the oracle uses it for a private GLC diagnostic) */
-    SPG_FLAG_FORCE_EIG = 2  /* always take the eigen-decomposition route of src/logdet_function.cpp:14-64
+    SPG_FLAG_FORCE_EIG = 2, /* always take the eigen-decomposition route of src/logdet_function.cpp:14-64
                                (default: the equivalent gauge/Cholesky route whenever its guard holds) */
+    SPG_FLAG_GLC_KLD = 4    /* GLC only: also compute the per-blanket KLD of every removal (the reference's GLC provider has no
+                               LogdetFunction and reports none). With A = sum_e (W_e G_e)^T (W_e G_e) over the emitted edges (G_e =
+                               the reparametrisation Jacobian), N^ the orthonormal gauge basis and C = Lambda_t + N^ N^^T:
+                                   kld = 1/2 (tr(C^-1 A) - log det(A + N^ N^^T) + log det C - (n - d)),
+                               src/logdet_function.cpp:119-133 at the GLC edges' information, the NFR branch's gauge route.
+                               Edges and statuses are bit-identical to an unflagged run; the value lands after the ready word,
+                               like the NFR one. Where it is not defined the blanket reports NaN + SPG_INFO_GLC_KLD_SKIPPED;
+                               the large-blanket pipeline (GLC Dense beyond the LDS kernel) never computes it. Backends other
+                               than the HIP one may ignore the flag. Clear (default): kld stays NaN for GLC. */
     /* bits 8..15: diagnostic pipeline truncation used by tools/phase_bench.py */
 };
 
@@ -123,7 +136,7 @@ typedef struct {
     double *new_edge_data;        /* same record layout as spg_batch.edge_data */
     int32_t new_edge_cap, new_edge_vert_cap;
     int64_t new_edge_data_cap;
-    double *kld;                  /* B */
+    double *kld;                  /* B : NFR: always (closed-form blankets); GLC: NaN unless SPG_FLAG_GLC_KLD is set */
     double *min_gap;              /* B, optional: smallest relative gap between consecutive Chow-Liu weights popped */
     int32_t *status;              /* B : SPG_ST_* */
     int32_t *info;                /* B, optional: SPG_INFO_* bits */
@@ -240,7 +253,7 @@ typedef struct {
     int32_t n_bad_status;  /* blankets with a status that is not SPG_OK / SPG_ST_KLD_NOT_PD */
     int32_t max_blanket;   /* largest k+m */
     int32_t n_launches;    /* kernel launches */
-    double kld_sum;        /* sum of finite per-blanket KLD */
+    double kld_sum;        /* sum of finite per-blanket KLD (GLC: 0 unless SPG_FLAG_GLC_KLD is set) */
     double host_seconds;   /* host scheduling + graph update */
     double device_seconds; /* time blocked on the device (launch -> results visible) */
     double schedule_seconds; /* part of host_seconds: conflict-free round selection */

@@ -360,7 +360,7 @@ public:
         so.topology = (int)o.topology;
         so.lin_point = (int)o.linPoint;
         so.include_intra_clique = o.includeIntraClique ? 1 : 0;
-        so.flags = 0;
+        so.flags = (_glc && _glc_kld) ? SPG_FLAG_GLC_KLD : 0;
         so.chord_ratio = o.chordRatio;
         std::vector<int32_t> w(which.begin(), which.end());
         drop_views();
@@ -539,7 +539,12 @@ public:
         return out;
     }
     // sum over blankets of LogdetFunction::value (src/logdet_function.cpp:119-133) of the last marginalize()
+    // (GLC graphs: 0 unless setGlcBlanketKld(true) was called before marginalize())
     double lastKullbackLeiblerSum() const { return _stats.kld_sum; }
+    // Per-blanket KLD of GLC removals (SPG_FLAG_GLC_KLD, include/spg.h): off by default, as in the reference, whose GLC
+    // provider has no LogdetFunction. No effect on an NFR graph. Not a member of the reference's SparsityOptions.
+    void setGlcBlanketKld(bool on) { _glc_kld = on; }
+    bool glcBlanketKld() const { return _glc_kld; }
     const spg_marg_stats &lastStats() const { return _stats; }
     spg_graph *handle() { return _g; }
     spg_ctx *context() { return _ctx->h; }
@@ -610,6 +615,7 @@ private:
     std::shared_ptr<Ctx> _ctx;
     spg_graph *_g = nullptr;
     bool _glc;
+    bool _glc_kld = false;
     spg_marg_stats _stats{};
     spg_optimize_stats _last_opt{};
     mutable std::vector<Vertex *> _vviews;     // id-sorted

@@ -16,8 +16,9 @@ EDGE_BINARY, EDGE_GLC, EDGE_MULTI = 0, 1, 2
 ST_OK, ST_HMM_NOT_PD, ST_EIG_FAIL, ST_NONFINITE, ST_TIKHONOV_NOT_PD, ST_CLOSED_FORM_NOT_PD, \
     ST_KLD_NOT_PD, ST_NEEDS_INTERIOR_POINT, ST_MARGINAL_NOT_PD, ST_EMPTY_BLANKET, ST_UNSUPPORTED, \
     ST_NEEDS_LOCAL_OPTIMIZATION = range(12)
-INFO_RANK_DEFICIENT, INFO_GLC_ROOT_EDGE, INFO_IP_HESSIAN_NOT_PD = 1, 2, 4
+INFO_RANK_DEFICIENT, INFO_GLC_ROOT_EDGE, INFO_IP_HESSIAN_NOT_PD, INFO_GLC_KLD_SKIPPED = 1, 2, 4, 8
 FLAG_FORCE_EIG = 2
+FLAG_GLC_KLD = 4
 EINVAL, ENODEV, ENOMEM, ECAPACITY, EHIP, EIO, ESTATE, EBLANKET, ENOTPD = -1, -2, -3, -4, -5, -6, -7, -8, -9
 OUT_HDR = 6
 
@@ -33,7 +34,10 @@ class Options(C.Structure):
 
 
 def make_options(pose_dim, algorithm=ALG_NFR, topology=TOPO_TREE, lin_point=LIN_GLOBAL, flags=0,
-                 chord_ratio=1.0, include_intra_clique=1):
+                 chord_ratio=1.0, include_intra_clique=1, glc_kld=False):
+    """glc_kld: SPG_FLAG_GLC_KLD — per-blanket KLD of GLC removals (kld is NaN for GLC without it)."""
+    if glc_kld:
+        flags |= FLAG_GLC_KLD
     return Options(pose_dim, algorithm, topology, lin_point, include_intra_clique, flags, chord_ratio)
 
 

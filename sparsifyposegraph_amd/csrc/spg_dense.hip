@@ -1110,9 +1110,10 @@ __global__ __launch_bounds__(256) void big_glc_eig_kernel(int *flags, const doub
     if (tid == 0) { flags[4] = 1; flags[5] = r; }
 }
 // out record of the blanket (layout in include/spg.h). flags / stats as above; partial[0..np) = sum of squares of L^-T
-// (trace of M_rel^-1); flags[4], flags[5] = outcome of the eigen route when the shortcut's guard failed.
+// (trace of M_rel^-1); flags[4], flags[5] = outcome of the eigen route when the shortcut's guard failed. info_bits: what the
+// caller wants in the info word (SPG_INFO_GLC_KLD_SKIPPED under SPG_FLAG_GLC_KLD: this pipeline computes no per-blanket KLD).
 __global__ void big_out_record_kernel(double *orec, const int *flags, const double *stats, const double *partial, int np, int n, int D_, int m, int k,
-                                      int n_new_max, int tag, long long rec_len) {
+                                      int n_new_max, int tag, long long rec_len, int info_bits) {
     __shared__ double red[256];
     double s = 0;
     for (int i = threadIdx.x; i < np; i += 256) s += partial[i];
@@ -1128,7 +1129,7 @@ __global__ void big_out_record_kernel(double *orec, const int *flags, const doub
         n_new = flags[5] > 0 ? 1 : 0;
         rec_len = (long long)n + (long long)flags[5] * n;
     }
-    orec[0] = (double)status; orec[1] = 0.0; orec[2] = __builtin_nan(""); orec[3] = __builtin_inf(); orec[4] = (double)n_new;
+    orec[0] = (double)status; orec[1] = (double)info_bits; orec[2] = __builtin_nan(""); orec[3] = __builtin_inf(); orec[4] = (double)n_new;
     if (n_new) {
         orec[SPG_OUT_HDR + 0] = (double)SPG_EDGE_GLC;
         orec[SPG_OUT_HDR + 1] = 0.0;
@@ -1394,7 +1395,7 @@ struct Carver {      // offsets into a block, 256-byte aligned
 // record (include/spg.h) to orec (device address: arena or pinned mailbox).
 template <int D>
 static int big_glc_dense_impl(hipStream_t s, const spg::DenseGraphIn &in, int m, int k, int Nm, int64_t new_off, double *orec, int n_new_max, int tag,
-                              double *seconds, char *err, size_t errlen) {
+                              int info_bits, double *seconds, char *err, size_t errlen) {
     constexpr int DD = D * D;
     const int n = D * k, nm = D * m, Ng = round_up(std::max(n, 1)), N = Nm + Ng, Nr = round_up(std::max(n - D, 1)), ntr = Nr / TB;
     double *arena = (double *)const_cast<void *>(in.dev_arena);
@@ -1495,7 +1496,7 @@ static int big_glc_dense_impl(hipStream_t s, const spg::DenseGraphIn &in, int m,
                            (const double *)Mt, Ng, n, n - D, Y, Vs, Ng, cs, perm, (const double *)meas, arena + new_off);
     }
     hipLaunchKernelGGL(big_out_record_kernel, dim3(1), dim3(256), 0, s, orec, (const int *)flags, (const double *)stats, (const double *)partial, np,
-                       n, D, m, k, n_new_max, tag, rec_len);
+                       n, D, m, k, n_new_max, tag, rec_len, info_bits);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(P.e1, s));
     HIPCHK(hipStreamSynchronize(s));   // the pool is laid out anew by the next call
@@ -1577,14 +1578,14 @@ void hip_big_release_scratch() {
 }
 
 int hip_big_glc_dense(void *stream, const DenseGraphIn &in, int m, int k, int Nm, int64_t new_off, double *orec, int n_new_max, int tag,
-                      double *seconds, double *flops, char *err, size_t errlen) {
+                      int info_bits, double *seconds, double *flops, char *err, size_t errlen) {
     const double n = (double)in.D * k, nm = (double)in.D * m, nr = n - in.D;
     // the n^3-class work on the matrix cores: H_mm Cholesky + panel solves + Schur update, M_rel Cholesky, L^-T
     if (flops) *flops = nm * nm * nm / 3.0 + nm * nm * n + nm * n * n + nr * nr * nr / 3.0 + nr * nr * nr / 3.0;
     static const bool trace = [] { const char *e = getenv("SPG_BIG_TRACE"); return e && e[0] == '1'; }();      // diagnostic: host time of a call next to its device time
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = by_dim(in.D, [&](auto d) {
-        return big_glc_dense_impl<decltype(d)::value>((hipStream_t)stream, in, m, k, Nm, new_off, orec, n_new_max, tag, seconds, err, errlen);
+        return big_glc_dense_impl<decltype(d)::value>((hipStream_t)stream, in, m, k, Nm, new_off, orec, n_new_max, tag, info_bits, seconds, err, errlen);
     });
     if (trace) fprintf(stderr, "big blanket n=%d nm=%d: call %.3f ms, device %.3f ms\n", (int)n, (int)nm,
                        1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), seconds ? 1e3 * *seconds : 0.0);

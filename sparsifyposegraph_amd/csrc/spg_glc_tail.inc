@@ -15,6 +15,103 @@
     // misc[3] = edges emitted, misc[4] = endpoints emitted, misc[5] = doubles emitted (packed offset)
     if (tid == 0) { misc[3] = 0; misc[4] = 0; misc[5] = 0; }
     T.sync();
+    double *Ng = smem + L.o_Ng;      // n x D orthonormal gauge basis (SPG_FLAG_GLC_KLD only)
+
+    // Per-blanket KLD of the emitted edges (SPG_FLAG_GLC_KLD), after the publish: the graph update does not wait for it.
+    // src/logdet_function.cpp:119-133 at the GLC edges' information, by the gauge route of the NFR branch (no inverse of a
+    // singular matrix, no eigen-decomposition): A = sum_e (W_e G_e)^T (W_e G_e) in emission order, C = Lambda_t + N^ N^^T,
+    //     kld = 1/2 ( tr(C^-1 A) - log det(A + N^ N^^T) + log det C - (n - D) ).
+    // M1 still holds Lambda_t (the tail above only reads it); M2, M3 and the batch buffers are free, the records are read
+    // back from the arena. Not defined — NaN and SPG_INFO_GLC_KLD_SKIPPED — when a root edge was emitted, when the edges
+    // carry other than n - D rows (the 1e-8 cut dropped an eigenvalue: A and Lambda_t no longer share a range), when
+    // trace(C^-1) >= 5e4 (the NFR route's guard) or when a factorisation fails. Below two kept vertices there is nothing
+    // to compare: NaN without the bit, as in the NFR branch; a blanket whose status is not SPG_OK keeps its words too.
+    auto glc_kld_tail = [&]() {
+        // a blanket that failed (status) or has nothing to compare (k < 2, no root edge) keeps NaN and its info word, but
+        // its record is complete as well: every flagged exit ends in the final word
+        const bool wanted = (status == SPG_OK) && !(k < 2 && !(info & SPG_INFO_GLC_ROOT_EDGE));
+        const int ng = misc[3];
+        bool defined = wanted && !(info & SPG_INFO_GLC_ROOT_EDGE);
+        int rows = 0;
+        for (int e = 0; e < ng; e++) rows += gmeta[3 * e + 1] / (D * gmeta[3 * e + 2]) - 1;
+        if (rows != n - D) defined = false;
+        double val = __builtin_nan("");
+        if (tid == 0) misc[0] = 0;
+        T.sync();
+        double ldC = 0.0, trC = 0.0;
+        if (defined) {
+            gauge_basis_raw<D>(T, pose + m * PSZ, k, Ng);
+            gauge_orthonormalise<D>(T, n, Ng, eT);
+            gauge_regularised<D>(T, M1, ld, n, Ng, M3);
+            // ---- C^-1 into M3, log det C, trace(C^-1)
+            if (use_wave) {
+                const bool ok_ = wave_spd_inverse(M3, ld, n, tid, 0.0, M3, ldC, trC);
+                defined = ok_ && (misc[0] == 0);
+                T.sync();
+            } else {
+                chol_lower<NT>(T, M3, n, ld, Sv);
+                defined = (misc[0] == 0);
+                T.sync();
+                if (defined) {
+                    ldC = chol_logdet<NT>(T, M3, n, ld);
+                    tri_inverse_lower<NT>(T, M3, M2, n, ld, Sv);
+                    gram_lower_inverse<NT>(T, M2, M3, n, ld);
+                    double d_ = 0;
+                    for (int i = tid; i < n; i += NT) d_ += M3[i * ld + i];
+                    trC = T.sum(d_);
+                }
+            }
+            if (!(trC < 5e4) || !isfinite(trC)) defined = false;
+        }
+        if (defined) {
+            for (int it = tid; it < n * ld; it += NT) M2[it] = 0.0;
+            T.sync();
+            double trp = 0;
+            int vp = 0;
+            for (int e = 0; e < ng; e++) {
+                const int q = gmeta[3 * e + 2], dq = D * q, re = gmeta[3 * e + 1] / dq - 1;
+                const int *vl = gverts + vp;
+                double *Aw = G + q * 2 * DD;      // re x dq, behind the Jacobians (<= 4 batch buffers: 2 n D + (n - D) n doubles)
+                glc_edge_rows(arena + bd.new_off + gmeta[3 * e + 0], q, re, vl, G, Aw);
+                for (int it = tid; it < dq * dq; it += NT) {
+                    const int R = it / dq, Cc = it - R * dq;
+                    double sacc = 0;
+                    for (int p = 0; p < re; p++) sacc += Aw[p * dq + R] * Aw[p * dq + Cc];
+                    M2[((vl[R / D] - m) * D + R % D) * ld + (vl[Cc / D] - m) * D + Cc % D] += sacc;
+                }
+                // tr(C^-1 A_e) = sum_p a_p C^-1 a_p^T over the rows a_p of W_e G_e
+                for (int it = tid; it < re * dq; it += NT) {
+                    const int p = it / dq, i = it - p * dq;
+                    const double *ci = M3 + ((vl[i / D] - m) * D + i % D) * ld;
+                    double sacc = 0;
+                    for (int j = 0; j < dq; j++) sacc += ci[(vl[j / D] - m) * D + j % D] * Aw[p * dq + j];
+                    trp += Aw[it] * sacc;
+                }
+                T.sync();
+                vp += q;
+            }
+            const double tr = T.sum(trp);
+            gauge_add<D>(T, M2, ld, n, Ng);
+            double ldA = 0.0;
+            if (use_wave) {
+                const bool ok_ = wave_spd_logdet(M2, ld, n, tid, ldA);
+                defined = ok_;
+            } else {
+                chol_lower<NT>(T, M2, n, ld);
+                defined = (misc[0] == 0);
+                T.sync();
+                if (defined) ldA = chol_logdet<NT>(T, M2, n, ld);
+            }
+            if (defined) val = 0.5 * (tr - ldA + ldC - (double)(n - D));
+        }
+        if (wanted && !defined) info |= SPG_INFO_GLC_KLD_SKIPPED;
+        // the record is complete: final word, after a release (include/spg.h)
+        if (tid == 0) {
+            orec[2] = val; orec[1] = (double)info;
+            __threadfence_system();
+            __hip_atomic_store(&orec[5], SPG_FINAL_WORD(a.tag), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    };
 
     auto finish_glc = [&]() {
         T.sync();
@@ -34,6 +131,7 @@
         __threadfence_system();
         T.sync();
         if (tid == 0) __hip_atomic_store(&orec[5], SPG_READY_WORD(a.tag), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (a.flags & SPG_FLAG_GLC_KLD) glc_kld_tail();
     };
 
     // Schur complement of Lambda_t onto the blocks keepb[0..nkeep) (ascending), others marginalised

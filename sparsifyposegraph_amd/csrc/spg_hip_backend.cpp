@@ -508,7 +508,9 @@ int HipBackend::run_big_blankets(Slot &S, const spg_round_desc *rd, void *arena,
         LocalGraph g(D, bd, rd, arena, rd->vert_pose_off + bd.vert_begin, [&](int l) { return l < m ? l * D : Nm + (l - m) * D; });
         double *orec = mail_dev ? (mail_dev + (bd.out_off - rd->mail_base)) : ((double *)arena + bd.out_off);
         double secs = 0, flops = 0;
-        if (int brc = hip_big_glc_dense((void *)S.stream, g.in, m, k, Nm, bd.new_off, orec, bd.n_new_max, rd->tag, &secs, &flops, err, sizeof err)) return brc;
+        // (no per-blanket KLD on this path: under SPG_FLAG_GLC_KLD the blanket says so in its info word)
+        const int info_bits = (rd->opts->flags & SPG_FLAG_GLC_KLD) ? SPG_INFO_GLC_KLD_SKIPPED : 0;
+        if (int brc = hip_big_glc_dense((void *)S.stream, g.in, m, k, Nm, bd.new_off, orec, bd.n_new_max, rd->tag, info_bits, &secs, &flops, err, sizeof err)) return brc;
         prof_big_ms += 1e3 * secs; prof_big_flops += flops; prof_big_count++;
         prof_big_nmax = std::max(prof_big_nmax, D * (k + m));
         S.wait_ev = nullptr;   // (as above: the slot is done when the stream is)

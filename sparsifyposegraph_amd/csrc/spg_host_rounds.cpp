@@ -566,7 +566,7 @@ static void submission_push(spg_graph *g, Batch &b) {
 }
 
 // Late results of a batch that was committed by polling: once its launch has completed, pick up the
-// per-blanket KLD (and a possible SPG_ST_KLD_NOT_PD) from the mailbox.
+// per-blanket KLD (and a possible SPG_ST_KLD_NOT_PD) from the mailbox — the NFR value, or the GLC one under SPG_FLAG_GLC_KLD.
 static int harvest_kld(spg_graph *g, Batch &bt) {
     if (bt.kld_pending.empty()) return 0;
     const bool slotted = g->ctx->be.synchronize_slot && g->ctx->be.mailbox_slot;
@@ -579,6 +579,7 @@ static int harvest_kld(spg_graph *g, Batch &bt) {
         lg.kld = rec[2];
         lg.min_gap = rec[3];
         lg.status = (int32_t)rec[0];
+        lg.info = (int32_t)rec[1];   // (SPG_INFO_GLC_KLD_SKIPPED is decided in the tail, after the ready word)
         if (std::isfinite(rec[2])) g->stats.kld_sum += rec[2];
     }
     bt.kld_pending.clear();

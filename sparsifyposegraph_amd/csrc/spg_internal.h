@@ -89,7 +89,7 @@ int hip_dense_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &ot
 
 // One GLC Dense blanket too large for the LDS kernel, dense in HBM on the fp64 matrix cores (spg_dense.hip)
 int hip_big_glc_dense(void *stream, const DenseGraphIn &local_graph, int m, int k, int Nm, int64_t new_off, double *orec, int n_new_max, int tag,
-                      double *seconds, double *flops, char *err, size_t errlen);
+                      int info_bits, double *seconds, double *flops, char *err, size_t errlen);
 // test harness of the generic kernel's workgroup linear algebra (csrc/spg_nfr_ip.hip: la_test_kernel), see spg_debug_la
 int hip_la_test(int op, int M, int N, int K, int flags, int mode, double *A, int ra, int lda, double *B, int rb, int ldb, double *C, int rc, int ldc, int *ok);
 // frees the scratch the large-blanket pipeline keeps between calls (device block + pinned staging); called when a backend goes

@@ -73,6 +73,123 @@ __device__ __forceinline__ void strec(double *p, double v) {
 }
 __device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// ---- gauge route, shared by the NFR information recovery and the GLC per-blanket KLD (SPG_FLAG_GLC_KLD)
+// Lambda_t of a blanket of relative measurements has an exactly known d-dimensional null space: the rigid motions of the
+// whole blanket, N = [G_1; ...; G_k] in the vertices' update coordinates. kpose = the kept vertices' poses (LDS form).
+template <int D, class TeamT>
+__device__ __forceinline__ void gauge_basis_raw(const TeamT TT, const double *kpose, int k, double *Ng) {
+    constexpr int DD = D * D, PSZ = (D == 6) ? 12 : 3;
+    for (int v = TT.tid; v < k; v += TT.size) {
+        const double *X = kpose + v * PSZ;
+        double *Gv = Ng + v * DD;
+        if (D == 6) {
+#pragma unroll
+            for (int rr = 0; rr < 3; rr++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    // R^T ; -R^T [t]x ; 0 ; 1/2 R^T   (column c of [t]x is t x e_c)
+                    constexpr int A1[3] = {1, 2, 0}, B1[3] = {2, 0, 1};
+                    const int ca = A1[c], cb = B1[c];
+                    double rt = X[c * 3 + rr];
+                    // (t x e_c): component cb = +t[ca]... derive: t x e_c = (t_a e_a + t_b e_b + t_c e_c) x e_c
+                    //   e_a x e_c = -e_b , e_b x e_c = +e_a   (a = c+1, b = c+2 cyclic)
+                    //   => t x e_c = t_b e_a - t_a e_b
+                    double cx_a = X[9 + cb], cx_b = -X[9 + ca];
+                    double val = -(X[ca * 3 + rr] * cx_a + X[cb * 3 + rr] * cx_b);  // -(R^T (t x e_c))[rr]
+                    Gv[rr * 6 + c] = rt;
+                    Gv[rr * 6 + 3 + c] = val;
+                    Gv[(3 + rr) * 6 + c] = 0.0;
+                    Gv[(3 + rr) * 6 + 3 + c] = 0.5 * rt;
+                }
+        } else {
+            Gv[0] = 1; Gv[1] = 0; Gv[2] = -X[1];
+            Gv[3] = 0; Gv[4] = 1; Gv[5] = X[0];
+            Gv[6] = 0; Gv[7] = 0; Gv[8] = 1;
+        }
+    }
+    TT.sync();
+}
+// orthonormalise: N^ = N L^-T with N^T N = L L^T (D x D, one lane, registers). scr: 2 D^2 doubles. Sets *TT.flag on failure.
+template <int D, class TeamT>
+__device__ __forceinline__ void gauge_orthonormalise(const TeamT TT, int n, double *Ng, double *scr) {
+    constexpr int DD = D * D;
+    if (TT.tid < DD) {
+        int rr = TT.tid / D, c = TT.tid - rr * D;
+        double s = 0;
+        for (int i = 0; i < n; i++) s += Ng[i * D + rr] * Ng[i * D + c];
+        scr[TT.tid] = s;
+    }
+    TT.sync();
+    if (TT.tid == 0) {
+        double Ab[DD], Li[DD];
+#pragma unroll
+        for (int i = 0; i < DD; i++) Ab[i] = scr[i];
+        if (!chol_reg<D>(Ab)) (*TT.flag) = 1;
+#pragma unroll
+        for (int c = 0; c < D; c++)
+#pragma unroll
+            for (int i = 0; i < D; i++) {
+                if (i < c) Li[i * D + c] = 0.0;
+                else if (i == c) Li[i * D + c] = 1.0 / Ab[c * D + c];
+                else {
+                    double s = 0;
+#pragma unroll
+                    for (int q = 0; q < D; q++) if (q >= c && q < i) s += Ab[i * D + q] * Li[q * D + c];
+                    Li[i * D + c] = -s / Ab[i * D + i];
+                }
+            }
+#pragma unroll
+        for (int i = 0; i < DD; i++) scr[DD + i] = Li[i];
+    }
+    TT.sync();
+    {
+        double nv_[D];
+        for (int i = TT.tid; i < n; i += TT.size) {
+#pragma unroll
+            for (int c = 0; c < D; c++) {
+                double s = 0;
+#pragma unroll
+                for (int q = 0; q < D; q++) if (q <= c) s += Ng[i * D + q] * scr[DD + c * D + q];
+                nv_[c] = s;
+            }
+#pragma unroll
+            for (int c = 0; c < D; c++) Ng[i * D + c] = nv_[c];
+        }
+    }
+    TT.sync();
+}
+// C = Lam + N^ N^^T (full symmetric) into Cm; Lam's lower triangle is read
+template <int D, class TeamT>
+__device__ __forceinline__ void gauge_regularised(const TeamT TT, const double *Lam, int ld, int n, const double *Ng, double *Cm) {
+    int sh = ceil_log2(n), tot = n << sh;
+    for (int it = TT.tid; it < tot; it += TT.size) {
+        int i = it >> sh, j = it & ((1 << sh) - 1);
+        if (j <= i) {
+            double s = Lam[i * ld + j];
+#pragma unroll
+            for (int q = 0; q < D; q++) s += Ng[i * D + q] * Ng[j * D + q];
+            Cm[i * ld + j] = s;
+            Cm[j * ld + i] = s;
+        }
+    }
+    TT.sync();
+}
+// Am += N^ N^^T, every entry
+template <int D, class TeamT>
+__device__ __forceinline__ void gauge_add(const TeamT TT, double *Am, int ld, int n, const double *Ng) {
+    int sh = ceil_log2(n), tot = n << sh;
+    for (int it = TT.tid; it < tot; it += TT.size) {
+        int i = it >> sh, j = it & ((1 << sh) - 1);
+        if (j < n) {
+            double s = 0;
+#pragma unroll
+            for (int q = 0; q < D; q++) s += Ng[i * D + q] * Ng[j * D + q];
+            Am[i * ld + j] += s;
+        }
+    }
+    TT.sync();
+}
+
 template <int D, int NT, bool GWS, int ALG, bool COH = false>
 __device__ __forceinline__ void blanket_body(const KArgs &a_in, const spg_blanket_desc &bd_in, const int64_t *bvpo_in, const spg_edge_ref *ber_in,
                                              const int32_t *bev_in, const int gws_slot, double *smem) {
@@ -595,45 +712,49 @@ __device__ __forceinline__ void blanket_body(const KArgs &a_in, const spg_blanke
     }
     }   // LM wrapper
     if (misc[1]) { status = SPG_ST_UNSUPPORTED; finish(); return; }
+    // Rows of one n-ary GLC edge in its vertices' update coordinates: Aw = W Jr (rr_ x D q), Jr = the reparametrisation
+    // Jacobian at the current estimates (src/glc_edge.cpp:40-49, src/glc_reparam_binary.hpp:78-127). rec = meas (D q) then
+    // W (rr_ x D q); vl = the edge's vertices as blanket-local indices; Jq = scratch of q x (Ji0 | Jii), 2 D^2 each.
+    auto glc_edge_rows = [&](const double *rec, int q, int rr_, const int *vl, double *Jq, double *Aw) {
+        const int dq = D * q;
+        for (int i = tid; i < q; i += NT) {
+            int v0 = vl[0], vi = vl[i];
+            if (D == 6) {
+                double Z[kIso], Xz[kIso] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+                iso_from_mqt(rec + 6 * i, Z);
+                if (i == 0) se3_edge_jac(Xz, pose + v0 * PSZ, Z, Jq, Jq + DD, nullptr);
+                else se3_edge_jac(pose + v0 * PSZ, pose + vi * PSZ, Z, Jq + i * 2 * DD, Jq + i * 2 * DD + DD, nullptr);
+            } else {
+                double xz[3] = {0, 0, 0};
+                if (i == 0) se2_edge_jac(xz, pose + v0 * PSZ, rec, Jq, Jq + DD, nullptr);
+                else se2_edge_jac(pose + v0 * PSZ, pose + vi * PSZ, rec + 3 * i, Jq + i * 2 * DD, Jq + i * 2 * DD + DD, nullptr);
+            }
+        }
+        T.sync();
+        for (int it = tid; it < rr_ * dq; it += NT) {
+            int row = it / dq, col = it - row * dq, blk = col / D, c = col - blk * D;
+            const double *Wr = rec + dq + (int64_t)row * dq;
+            double sacc = 0;
+            if (blk == 0) {
+                for (int p = 0; p < D; p++) sacc += Wr[p] * Jq[DD + p * D + c];            // W_0 * J00 (Jj of the mock edge)
+                for (int i = 1; i < q; i++)
+                    for (int p = 0; p < D; p++) sacc += Wr[i * D + p] * Jq[i * 2 * DD + p * D + c];  // W_i * Ji0
+            } else {
+                for (int p = 0; p < D; p++) sacc += Wr[blk * D + p] * Jq[blk * 2 * DD + DD + p * D + c];  // W_i * Jii
+            }
+            Aw[it] = sacc;
+        }
+        T.sync();
+    };
     if constexpr (is_glc) {
-        // n-ary GLC edges already in the blanket (a14): H += (W Jr)^T (W Jr), Jr = reparametrisation
-        // Jacobian at the current estimates (src/glc_edge.cpp:40-49, src/glc_reparam_binary.hpp:78-127)
+        // n-ary GLC edges already in the blanket (a14): H += (W Jr)^T (W Jr)
         double *gA = mat + L.o_gA;
         for (int e = 0; e < bd.n_edge; e++) {
             const spg_edge_ref er = ber[e];
             if (er.kind != SPG_EDGE_GLC) continue;
             const int q = er.nv, dq = D * q, rr_ = (er.len - dq) / dq;
-            const double *rec = arena + er.off;   // meas (dq) then W (rr_ x dq)
-            double *Jb = gA;                      // q x (Ji0 | Jii), 2*DD each
-            double *Aw = gA + q * 2 * DD;         // rr_ x dq
-            for (int i = tid; i < q; i += NT) {
-                int v0 = bev[er.vbegin], vi = bev[er.vbegin + i];
-                if (D == 6) {
-                    double Z[kIso], Xz[kIso] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-                    iso_from_mqt(rec + 6 * i, Z);
-                    if (i == 0) se3_edge_jac(Xz, pose + v0 * PSZ, Z, Jb, Jb + DD, nullptr);
-                    else se3_edge_jac(pose + v0 * PSZ, pose + vi * PSZ, Z, Jb + i * 2 * DD, Jb + i * 2 * DD + DD, nullptr);
-                } else {
-                    double xz[3] = {0, 0, 0};
-                    if (i == 0) se2_edge_jac(xz, pose + v0 * PSZ, rec, Jb, Jb + DD, nullptr);
-                    else se2_edge_jac(pose + v0 * PSZ, pose + vi * PSZ, rec + 3 * i, Jb + i * 2 * DD, Jb + i * 2 * DD + DD, nullptr);
-                }
-            }
-            T.sync();
-            for (int it = tid; it < rr_ * dq; it += NT) {
-                int row = it / dq, col = it - row * dq, blk = col / D, c = col - blk * D;
-                const double *Wr = rec + dq + (int64_t)row * dq;
-                double sacc = 0;
-                if (blk == 0) {
-                    for (int p = 0; p < D; p++) sacc += Wr[p] * Jb[DD + p * D + c];            // W_0 * J00 (Jj of the mock edge)
-                    for (int i = 1; i < q; i++)
-                        for (int p = 0; p < D; p++) sacc += Wr[i * D + p] * Jb[i * 2 * DD + p * D + c];  // W_i * Ji0
-                } else {
-                    for (int p = 0; p < D; p++) sacc += Wr[blk * D + p] * Jb[blk * 2 * DD + DD + p * D + c];  // W_i * Jii
-                }
-                Aw[it] = sacc;
-            }
-            T.sync();
+            double *Aw = gA + q * 2 * DD;         // rr_ x dq, behind the Jacobians
+            glc_edge_rows(arena + er.off, q, rr_, bev + er.vbegin, gA, Aw);
             for (int it = tid; it < dq * dq; it += NT) {
                 int R = it / dq, Cc = it - R * dq;
                 double sacc = 0;
@@ -872,98 +993,12 @@ __device__ __forceinline__ void blanket_body(const KArgs &a_in, const spg_blanke
     double logdetS = 0.0;
     double *Sg = M1, *Scr = M3;      // Sigma and scratch for the closed form (swapped on the gauge route)
     auto gauge_chain = [&](const auto TT) {
-        // ---- gauge basis
-        for (int v = TT.tid; v < k; v += TT.size) {
-            const double *X = pose + (m + v) * PSZ;
-            double *Gv = Ng + v * DD;
-            if (D == 6) {
-#pragma unroll
-                for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) {
-                        // R^T ; -R^T [t]x ; 0 ; 1/2 R^T   (column c of [t]x is t x e_c)
-                        constexpr int A1[3] = {1, 2, 0}, B1[3] = {2, 0, 1};
-                        const int ca = A1[c], cb = B1[c];
-                        double rt = X[c * 3 + rr];
-                        // (t x e_c): component cb = +t[ca]... derive: t x e_c = (t_a e_a + t_b e_b + t_c e_c) x e_c
-                        //   e_a x e_c = -e_b , e_b x e_c = +e_a   (a = c+1, b = c+2 cyclic)
-                        //   => t x e_c = t_b e_a - t_a e_b
-                        double cx_a = X[9 + cb], cx_b = -X[9 + ca];
-                        double val = -(X[ca * 3 + rr] * cx_a + X[cb * 3 + rr] * cx_b);  // -(R^T (t x e_c))[rr]
-                        Gv[rr * 6 + c] = rt;
-                        Gv[rr * 6 + 3 + c] = val;
-                        Gv[(3 + rr) * 6 + c] = 0.0;
-                        Gv[(3 + rr) * 6 + 3 + c] = 0.5 * rt;
-                    }
-            } else {
-                Gv[0] = 1; Gv[1] = 0; Gv[2] = -X[1];
-                Gv[3] = 0; Gv[4] = 1; Gv[5] = X[0];
-                Gv[6] = 0; Gv[7] = 0; Gv[8] = 1;
-            }
-        }
-        TT.sync();
+        gauge_basis_raw<D>(TT, pose + m * PSZ, k, Ng);
         CSTAMP(11);  // gauge basis
-        // ---- orthonormalise: N^ = N L^-T with N^T N = L L^T (D x D, one lane, registers)
-        if (TT.tid < DD) {
-            int rr = TT.tid / D, c = TT.tid - rr * D;
-            double s = 0;
-            for (int i = 0; i < n; i++) s += Ng[i * D + rr] * Ng[i * D + c];
-            eT[TT.tid] = s;
-        }
-        TT.sync();
-        if (TT.tid == 0) {
-            double Ab[DD], Li[DD];
-#pragma unroll
-            for (int i = 0; i < DD; i++) Ab[i] = eT[i];
-            if (!chol_reg<D>(Ab)) (*TT.flag) = 1;
-#pragma unroll
-            for (int c = 0; c < D; c++)
-#pragma unroll
-                for (int i = 0; i < D; i++) {
-                    if (i < c) Li[i * D + c] = 0.0;
-                    else if (i == c) Li[i * D + c] = 1.0 / Ab[c * D + c];
-                    else {
-                        double s = 0;
-#pragma unroll
-                        for (int q = 0; q < D; q++) if (q >= c && q < i) s += Ab[i * D + q] * Li[q * D + c];
-                        Li[i * D + c] = -s / Ab[i * D + i];
-                    }
-                }
-#pragma unroll
-            for (int i = 0; i < DD; i++) eT[DD + i] = Li[i];
-        }
-        TT.sync();
-        {
-            double nv_[D];
-            for (int i = TT.tid; i < n; i += TT.size) {
-#pragma unroll
-                for (int c = 0; c < D; c++) {
-                    double s = 0;
-#pragma unroll
-                    for (int q = 0; q < D; q++) if (q <= c) s += Ng[i * D + q] * eT[DD + c * D + q];
-                    nv_[c] = s;
-                }
-#pragma unroll
-                for (int c = 0; c < D; c++) Ng[i * D + c] = nv_[c];
-            }
-        }
-        TT.sync();
+        gauge_orthonormalise<D>(TT, n, Ng, eT);
         CSTAMP(12);  // orthonormalised
         // ---- C = Lambda_t + N^ N^^T into M3, Cholesky, inverse
-        {
-            int sh = ceil_log2(n), tot = n << sh;
-            for (int it = TT.tid; it < tot; it += TT.size) {
-                int i = it >> sh, j = it & ((1 << sh) - 1);
-                if (j <= i) {
-                    double s = M1[i * ld + j];
-#pragma unroll
-                    for (int q = 0; q < D; q++) s += Ng[i * D + q] * Ng[j * D + q];
-                    M3[i * ld + j] = s;
-                    M3[j * ld + i] = s;
-                }
-            }
-            TT.sync();
-        }
+        gauge_regularised<D>(TT, M1, ld, n, Ng, M3);
         CSTAMP(13);  // C formed
         if ((use_wave_hw && TT.size == 64)) {
             double ldC, trC;
@@ -1249,17 +1284,7 @@ __device__ __forceinline__ void blanket_body(const KArgs &a_in, const spg_blanke
         STAMP(19);  // A assembled
         if (gauge_ok) {
             // kld = 1/2 ( tr(C^-1 A) - log det(A + N^ N^^T) + log det C - r ), tr(C^-1 A) = sum_e tr(X_e B_e)
-            int sh = ceil_log2(n), tot = n << sh;
-            for (int it = tid; it < tot; it += NT) {
-                int i = it >> sh, j = it & ((1 << sh) - 1);
-                if (j < n) {
-                    double s = 0;
-#pragma unroll
-                    for (int q = 0; q < D; q++) s += Ng[i * D + q] * Ng[j * D + q];
-                    Am[i * ld + j] += s;
-                }
-            }
-            T.sync();
+            gauge_add<D>(T, Am, ld, n, Ng);
             double tr;
             {
                 double s = 0;

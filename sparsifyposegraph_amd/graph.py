@@ -77,6 +77,7 @@ class GraphWrapperHIP:
         self.h = _handle
         self.d = self.L.spg_graph_pose_dim(self.h)
         self.last_stats = None
+        self.glcBlanketKld = False   # setGlcBlanketKld
         self.ctx._track(self)
 
     # ---- construction -------------------------------------------------------------------
@@ -131,10 +132,19 @@ class GraphWrapperHIP:
         check(self.L.spg_graph_set_estimate(self.h, int(vertexid), _p(est, C.c_double)), self.ctx.h, "setEstimate")
 
     # ---- the hot path -------------------------------------------------------------------
+    def setGlcBlanketKld(self, on=True):
+        """Per-blanket KLD of GLC removals (SPG_FLAG_GLC_KLD, include/spg.h) in blankets()["kld"] and kld_sum for the
+        marginalisations that follow; off by default, as in the reference. Only applies to SparsityOptions arguments of a
+        useGLC graph: an abi.Options argument carries its own flags (abi.make_options(..., glc_kld=True))."""
+        self.glcBlanketKld = bool(on)
+
+    def _flags(self, flags):
+        return flags | (abi.FLAG_GLC_KLD if (self.useGLC and self.glcBlanketKld) else 0)
+
     def marginalizeNoOptimize(self, which, options, flags=0):
         """src/graph_wrapper_g2o.cpp:398-453"""
         which = np.ascontiguousarray(which, np.int32)
-        o = options.to_abi(self.d, self.useGLC, flags) if isinstance(options, SparsityOptions) else options
+        o = options.to_abi(self.d, self.useGLC, self._flags(flags)) if isinstance(options, SparsityOptions) else options
         st = abi.MargStats()
         rc = self.L.spg_graph_marginalize(self.h, _p(which, C.c_int32), len(which), C.byref(o), C.byref(st))
         self.last_stats = st.asdict()
@@ -145,7 +155,7 @@ class GraphWrapperHIP:
         """spg_graph_marginalize_ranks with the library's built-in exchange (the context's RCCL communicator,
         Context.ranks): every rank calls this with identical arguments on an identical replica."""
         which = np.ascontiguousarray(which, np.int32)
-        o = options.to_abi(self.d, self.useGLC, flags) if isinstance(options, SparsityOptions) else options
+        o = options.to_abi(self.d, self.useGLC, self._flags(flags)) if isinstance(options, SparsityOptions) else options
         st = abi.MargStats()
         rc = self.L.spg_graph_marginalize_ranks(self.h, _p(which, C.c_int32), len(which), C.byref(o), int(rank), int(nranks), None, None, C.byref(st))
         self.last_stats = st.asdict()
