@@ -310,6 +310,21 @@ int spg_graph_substitute_edge(spg_graph *g, const int32_t *marginalized, int n_m
  * (fixed_id < 0: the smallest id, which is the vertex the reference fixes and skips), id order,
  * n = pose_dim * (V - 1). Returns n; the n x n row-major matrix is written if cap >= n*n. */
 int64_t spg_graph_information(spg_graph *g, int32_t fixed_id, double *out, int64_t cap);
+/* The same matrix in block-CSR form at any size (GraphWrapperG2O::sparseInformation, src/graph_wrapper_g2o.cpp:382-396):
+ * D x D row-major blocks; block rows and columns are the live vertices except the fixed one in ascending id order (the
+ * conventions of spg_graph_information); the full symmetric pattern (both triangles), columns ascending within a row,
+ * the diagonal block always present. A binary edge contributes its pair, a GLC or MULTI edge the clique of its
+ * vertices, a self-loop nothing; parallel edges accumulate into one block. Block (u, v) is the transpose of block
+ * (v, u) bit for bit, and the values equal those of spg_graph_information. Returns the number of blocks nnzb; the arrays
+ * (row_ptr: nb + 1, col_idx: nnzb, blocks: nnzb D^2 doubles, ids: nb vertex ids, may be NULL) are written only when
+ * row_ptr and col_idx are given and cap_blocks >= nnzb. blocks == NULL: the pattern only — host work, any backend.
+ * Arguments are checked (SPG_EINVAL) before the backend; values need the HIP backend (SPG_ESTATE); the only size limit
+ * is free device memory (SPG_ECAPACITY). */
+int64_t spg_graph_sparse_information(spg_graph *g, int32_t fixed_id, int64_t *row_ptr, int32_t *col_idx, double *blocks,
+                                     int64_t cap_blocks, int32_t *ids);
+/* Y = H X with that matrix, which is assembled block-CSR on the device and never formed densely: X and Y hold nrhs
+ * vectors of length n = D nb, one after the other. Same checks and error codes. */
+int spg_graph_information_apply(spg_graph *g, int32_t fixed_id, const double *X, int nrhs, double *Y);
 /* kullbackLeiblerDivergence(diff, infox, maty, InformationInformation) (src/utils.cpp:70-97):
  * kld = 0.5 * (innerprod + mahalanobis - logdetx - logdety - n), logdety = -sum log D(maty). */
 typedef struct {
@@ -400,17 +415,33 @@ int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, cons
  * chi2): dense (blocked fp64-MFMA Cholesky) up to 12 k scalar variables, block-sparse multifrontal (nested
  * dissection on the host, fronts on the matrix cores: CHOLMOD's role) beyond — see spg_ctx_set_linear_solver.
  * The estimates of the graph are updated in place. */
-enum { SPG_SOLVER_AUTO = 0, SPG_SOLVER_DENSE = 1, SPG_SOLVER_SPARSE = 2 };
+enum { SPG_SOLVER_AUTO = 0, SPG_SOLVER_DENSE = 1, SPG_SOLVER_SPARSE = 2, SPG_SOLVER_PCG = 3 };
 /* Which factorisation spg_graph_optimize / _optimize_fixed / _kullback_leibler of graphs of this context use.
  * AUTO (default): by size. DENSE beyond its capacity (32 k / 46 k variables) returns SPG_ECAPACITY. The covariance
- * blocks (spg_graph_marginal_covariances / _joint_covariances / _marginal_kld) are always block-sparse. */
+ * blocks (spg_graph_marginal_covariances / _joint_covariances / _marginal_kld) are always block-sparse.
+ * PCG (g2o's third solver family; AUTO never chooses it): spg_graph_optimize / _optimize_fixed solve each LM trial
+ * (H + lambda I) x = b by block-Jacobi preconditioned conjugate gradients on the block-CSR matrix of
+ * spg_graph_sparse_information, without a factorisation. A solve that does not reach the tolerance is not an error: its
+ * iterate is an inexact LM step, guarded by LM's gain test and counted in spg_pcg_stats. The KLD calls need log
+ * determinants and the covariance calls the factor: both treat PCG as AUTO. */
 int spg_ctx_set_linear_solver(spg_ctx *ctx, int solver);
+/* PCG parameters of the context: stop at ||r|| <= rel_tol ||b|| or after max_iter iterations. <= 0: the defaults,
+ * rel_tol = 1e-10 and max_iter = min(n, 20000) (g2o iterates up to n). */
+int spg_ctx_set_pcg(spg_ctx *ctx, double rel_tol, int max_iter);
+typedef struct {
+    int32_t solves, unconverged;         /* linear systems solved by PCG; those that stopped at max_iter */
+    int64_t iterations;                  /* CG iterations over all solves */
+    double last_rel_residual;            /* ||r|| / ||b|| of the recurrence at the end of the last solve */
+    double solve_seconds;                /* host time of the solves (they end with a synchronisation) */
+} spg_pcg_stats;
+/* of the last spg_graph_optimize / _optimize_fixed call of the context (all zero if it did not run PCG) */
+int spg_ctx_pcg_stats(spg_ctx *ctx, spg_pcg_stats *out);
 typedef struct {
     int32_t iterations, trials;          /* LM iterations run; linear systems solved */
     double chi2_initial, chi2_final, lambda_final;
     int64_t n;                           /* scalar variables */
     double device_seconds;
-    int32_t solver;                      /* SPG_SOLVER_DENSE or SPG_SOLVER_SPARSE: what ran */
+    int32_t solver;                      /* SPG_SOLVER_DENSE, SPG_SOLVER_SPARSE or SPG_SOLVER_PCG: what ran */
     int32_t supernodes;                  /* sparse: fronts of the assembly tree */
     double front_bytes;                  /* sparse: bytes of fronts in HBM */
     double factor_flops;                 /* sparse: flops of one factorisation */

@@ -281,7 +281,11 @@ public:
     // default: by size) — CHOLMOD's / SimplicialLLT's role in src/graph_wrapper_g2o.cpp:250-269,531-548
     // arena capacity up front + the host-side buffers of a marginalisation sized and touched (include/spg.h: spg_graph_reserve)
     void reserve(long long arena_doubles) { check(spg_graph_reserve(_g, arena_doubles), "spg_graph_reserve"); }
+    enum LinearSolver { SolverAuto = SPG_SOLVER_AUTO, SolverDense = SPG_SOLVER_DENSE, SolverSparse = SPG_SOLVER_SPARSE, SolverPCG = SPG_SOLVER_PCG };
     void setLinearSolver(int solver) { check(spg_ctx_set_linear_solver(_ctx->h, solver), "spg_ctx_set_linear_solver"); }
+    // SolverPCG: tolerance on ||r|| / ||b|| and iteration cap of each solve (<= 0: defaults); counters of the last optimize()
+    void setPcg(double rel_tol, int max_iter) { check(spg_ctx_set_pcg(_ctx->h, rel_tol, max_iter), "spg_ctx_set_pcg"); }
+    spg_pcg_stats pcgStats() const { spg_pcg_stats st{}; check(spg_ctx_pcg_stats(_ctx->h, &st), "spg_ctx_pcg_stats"); return st; }
     GraphWrapperHIP(const GraphWrapperHIP &) = delete;
     GraphWrapperHIP &operator=(const GraphWrapperHIP &) = delete;
     ~GraphWrapperHIP() override {
@@ -343,6 +347,45 @@ public:
         MatrixXd H((int)n, (int)n);
         check((int)std::min<int64_t>(spg_graph_information(_g, -1, H.data(), n * n), 0), "information");
         return H;
+    }
+    // GraphWrapperG2O::sparseInformation (src/graph_wrapper_g2o.cpp:382-396): information() in block-CSR form at any size.
+    // D x D row-major blocks, both triangles, columns ascending within a row; ids names the block rows (ascending).
+    struct BlockCSR {
+        int blockDim = 0;
+        std::vector<int64_t> rowPtr;     // rows() + 1
+        std::vector<int32_t> colIdx;     // blocks()
+        std::vector<double> values;      // blocks() * blockDim^2; empty for a pattern-only export
+        std::vector<int32_t> ids;        // vertex id of each block row
+        int rows() const { return (int)ids.size(); }
+        int64_t blocks() const { return (int64_t)colIdx.size(); }
+    };
+    void sparseInformation(BlockCSR &out, int fixed_id = -1, bool values = true) {
+        const int d = spg_graph_pose_dim(_g);
+        const int64_t nnzb = spg_graph_sparse_information(_g, fixed_id, nullptr, nullptr, nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(nnzb, 0), "sparseInformation");
+        const int nb = std::max(spg_graph_num_vertices(_g) - 1, 0);
+        out.blockDim = d;
+        out.rowPtr.assign((size_t)nb + 1, 0);
+        out.colIdx.assign((size_t)nnzb, 0);
+        out.values.assign(values ? (size_t)nnzb * d * d : 0, 0.0);
+        out.ids.assign((size_t)nb, 0);
+        std::vector<int32_t> col((size_t)std::max<int64_t>(nnzb, 1));
+        std::vector<double> val(values ? (size_t)std::max<int64_t>(nnzb, 1) * d * d : 0);
+        std::vector<int32_t> ids((size_t)std::max(nb, 1));
+        check((int)std::min<int64_t>(spg_graph_sparse_information(_g, fixed_id, out.rowPtr.data(), col.data(), values ? val.data() : nullptr, nnzb, ids.data()), 0),
+              "sparseInformation");
+        std::copy(col.begin(), col.begin() + nnzb, out.colIdx.begin());
+        std::copy(val.begin(), val.begin() + out.values.size(), out.values.begin());
+        std::copy(ids.begin(), ids.begin() + nb, out.ids.begin());
+    }
+    // Y = information() * X without forming the matrix densely; X holds nrhs vectors of length d * (vertices - 1), one
+    // after the other, and so does the result
+    std::vector<double> informationApply(const std::vector<double> &X, int nrhs = 1, int fixed_id = -1) {
+        const size_t n = (size_t)spg_graph_pose_dim(_g) * (size_t)std::max(spg_graph_num_vertices(_g) - 1, 0);
+        if (nrhs <= 0 || X.size() != n * (size_t)nrhs) throw std::runtime_error("informationApply: X must hold nrhs vectors of d * (vertices - 1) numbers");
+        std::vector<double> Y(X.size(), 0.0);
+        if (n > 0) check(spg_graph_information_apply(_g, fixed_id, X.data(), nrhs, Y.data()), "informationApply");
+        return Y;
     }
     // GraphWrapperG2O::covariance (src/graph_wrapper_g2o.cpp:368-373)
     MatrixXd covariance() override {

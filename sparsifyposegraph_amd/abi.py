@@ -113,7 +113,16 @@ class SparsePlanInfo(C.Structure):
                 ("n_rows", C.c_int64), ("front_bytes", C.c_double), ("flops", C.c_double)]
 
 
-SOLVER_AUTO, SOLVER_DENSE, SOLVER_SPARSE = 0, 1, 2
+SOLVER_AUTO, SOLVER_DENSE, SOLVER_SPARSE, SOLVER_PCG = 0, 1, 2, 3
+
+
+class PcgStats(C.Structure):
+    """spg_pcg_stats (include/spg.h)"""
+    _fields_ = [("solves", C.c_int32), ("unconverged", C.c_int32), ("iterations", C.c_int64),
+                ("last_rel_residual", C.c_double), ("solve_seconds", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class RoundInfo(C.Structure):

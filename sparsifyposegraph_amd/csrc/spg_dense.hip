@@ -1835,3 +1835,4 @@ int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iteratio
 }  // namespace spg
 
 #include "spg_sparse.inc"
+#include "spg_bsr.inc"

@@ -125,6 +125,9 @@ struct spg_ctx {
     void *rccl = nullptr;         // communicator handle of csrc/spg_rccl.cpp (nullptr: single rank / no id given)
     int tag_counter = 0;          // ready tags are unique per context (its mailboxes are shared by all graphs)
     int linear_solver = 0;        // SPG_SOLVER_*: dense / block-sparse factorisation for optimize() and the global KLD
+    double pcg_rel_tol = 0;       // spg_ctx_set_pcg; <= 0: the defaults (1e-10, min(n, 20000))
+    int pcg_max_iter = 0;
+    spg_pcg_stats pcg_stats{};    // of the last optimize call
     spg::StreamPort *sim_port = nullptr;   // tools/host_sim.cpp only: a simulated persistent worker behind an injected backend
     char err[768] = {0};
 };

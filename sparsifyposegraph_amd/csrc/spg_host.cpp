@@ -100,8 +100,19 @@ extern "C" int spg_ctx_create_ranks(spg_ctx **out, int device, int rank, int nra
     return 0;
 }
 extern "C" int spg_ctx_set_linear_solver(spg_ctx *c, int solver) {
-    if (!c || solver < SPG_SOLVER_AUTO || solver > SPG_SOLVER_SPARSE) return SPG_EINVAL;
+    if (!c || solver < SPG_SOLVER_AUTO || solver > SPG_SOLVER_PCG) return SPG_EINVAL;
     c->linear_solver = solver;
+    return 0;
+}
+extern "C" int spg_ctx_set_pcg(spg_ctx *c, double rel_tol, int max_iter) {
+    if (!c || std::isnan(rel_tol)) return SPG_EINVAL;
+    c->pcg_rel_tol = rel_tol > 0 ? rel_tol : 0;
+    c->pcg_max_iter = max_iter > 0 ? max_iter : 0;
+    return 0;
+}
+extern "C" int spg_ctx_pcg_stats(spg_ctx *c, spg_pcg_stats *out) {
+    if (!c || !out) return SPG_EINVAL;
+    *out = c->pcg_stats;
     return 0;
 }
 

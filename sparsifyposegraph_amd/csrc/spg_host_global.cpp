@@ -1,8 +1,9 @@
 // csrc/spg_host_global.cpp — the entry points of include/spg.h that work on a whole graph at once (global KLD,
-// information, covariance and its blocks, optimize / chi2, the symbolic plan): the graph is staged on the host as one
+// information (dense and block-CSR) and its product, covariance and its blocks, optimize / chi2, the symbolic plan): the graph is staged on the host as one
 // DenseGraphIn and handed to the device drivers of spg_dense.hip / spg_sparse.inc. Nothing here touches the scheduler.
 #include "spg_graph_impl.h"
 #include "spg_sparse_plan.hpp"
+#include "spg_bsr_pattern.hpp"
 
 // ================================================================================= global KLD (a18)
 namespace {
@@ -98,6 +99,72 @@ extern "C" int64_t spg_graph_information(spg_graph *g, int32_t fixed_id, double 
     return dense_matrix(g, fixed_id, out, cap, spg::hip_dense_information, 0, "spg_graph_information");
 }
 
+// ================================================================================= block-CSR information, H X
+namespace {
+// What the two calls share: the fixed vertex resolved, the free vertices staged with pos = D * block row (host work
+// only unless `device`: then the device holds the graph and is idle) and the pattern of that numbering.
+int bsr_stage(spg_graph *g, int32_t fixed_id, bool device, const char *what, std::vector<int32_t> &order, int &fixed, DenseStage &st,
+              spg::bsr::Pattern &P) {
+    order = live_vertices_by_id(g);
+    fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    if (device) {
+        if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "%s needs the HIP backend", what);
+        if (int rc = stage_global(g, order, {fixed}, g->d, st)) return rc;
+    } else {
+        stage_free_vertices(g, order, {fixed}, g->d, st);
+    }
+    spg::bsr::build_pattern(st.in.nv, st.in.pos, g->d, st.in.ne, st.in.er, st.in.ev, P);
+    return 0;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_sparse_information(spg_graph *g, int32_t fixed_id, int64_t *row_ptr, int32_t *col_idx, double *blocks,
+                                                int64_t cap_blocks, int32_t *ids) {
+    if (!g || g->active || cap_blocks < 0) return SPG_EINVAL;
+    std::vector<int32_t> order;
+    int fixed = -1;
+    DenseStage st;
+    spg::bsr::Pattern P;
+    const bool values = blocks && row_ptr && col_idx;
+    if (int rc = bsr_stage(g, fixed_id, false, "spg_graph_sparse_information", order, fixed, st, P)) return rc;
+    const int64_t nnzb = P.nnzb();
+    if (!row_ptr || !col_idx || cap_blocks < nnzb) return nnzb;
+    if (values) {
+        // the device copy of the graph may move when it is brought up to date: stage again once it is
+        DenseStage sd;
+        if (int rc = bsr_stage(g, fixed_id, true, "spg_graph_sparse_information", order, fixed, sd, P)) return rc;
+        if (int rc = spg::hip_bsr_information(spg::hip_backend_stream(&g->ctx->be), sd.in, P, blocks, g->ctx->err, sizeof g->ctx->err)) return rc;
+    }
+    std::copy(P.row_ptr.begin(), P.row_ptr.end(), row_ptr);
+    std::copy(P.col.begin(), P.col.end(), col_idx);
+    if (ids) {
+        int32_t *o = ids;
+        for (int32_t v : order) if (v != fixed) *o++ = g->vid[v];
+    }
+    return nnzb;
+}
+
+extern "C" int spg_graph_information_apply(spg_graph *g, int32_t fixed_id, const double *X, int nrhs, double *Y) {
+    if (!g || g->active || !X || !Y || nrhs <= 0) return SPG_EINVAL;
+    std::vector<int32_t> order;
+    int fixed = -1;
+    DenseStage st;
+    spg::bsr::Pattern P;
+    if (int rc = bsr_stage(g, fixed_id, true, "spg_graph_information_apply", order, fixed, st, P)) return rc;
+    return spg::hip_bsr_apply(spg::hip_backend_stream(&g->ctx->be), st.in, P, X, nrhs, Y, g->ctx->err, sizeof g->ctx->err);
+}
+
+extern "C" int spg_debug_bsr_bench(spg_graph *g, int32_t fixed_id, int reps, double *out) {
+    if (!g || g->active || !out || reps <= 0) return SPG_EINVAL;
+    std::vector<int32_t> order;
+    int fixed = -1;
+    DenseStage st;
+    spg::bsr::Pattern P;
+    if (int rc = bsr_stage(g, fixed_id, true, "spg_debug_bsr_bench", order, fixed, st, P)) return rc;
+    return spg::hip_bsr_bench(spg::hip_backend_stream(&g->ctx->be), st.in, P, reps, out, g->ctx->err, sizeof g->ctx->err);
+}
+
 extern "C" int64_t spg_graph_covariance(spg_graph *g, int32_t fixed_id, double *out, int64_t cap) {
     return dense_matrix(g, fixed_id, out, cap, spg::hip_dense_covariance, 46000, "spg_graph_covariance");
 }
@@ -135,7 +202,9 @@ extern "C" int spg_graph_kullback_leibler(spg_graph *base, spg_graph *other, int
     if (kept_b.empty()) return set_err(ctx, SPG_EINVAL, "spg_graph_kullback_leibler: no common free vertex");
     const int64_t n_marg = (int64_t)d * marg_b.size(), n_keep = (int64_t)d * kept_b.size();
     const int64_t Nm = (n_marg + 63) / 64 * 64, Ng = (n_keep + 63) / 64 * 64;
-    const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && Nm + Ng > 46000);
+    // (PCG yields no log-determinant: the KLD treats it as AUTO)
+    const int solver = ctx->linear_solver == SPG_SOLVER_PCG ? (int)SPG_SOLVER_AUTO : ctx->linear_solver;
+    const bool sparse = solver == SPG_SOLVER_SPARSE || (solver == SPG_SOLVER_AUTO && Nm + Ng > 46000);
     if (!sparse && Nm + Ng > 46000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_kullback_leibler: dense formulation limited to 46k variables (16 GB)");
     if (int rc = sync_device(base)) return rc;
     if (int rc = sync_device(other)) return rc;
@@ -398,16 +467,29 @@ static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<i
     for (int32_t v : fixed_vertices) is_fixed[v] = 1;
     int64_t n = 0;
     for (int32_t v : order) if (!is_fixed[v]) n += g->d;
-    // dense up to 12 k unknowns (two n^2 matrices, an n^3 / 3 factorisation per trial), block-sparse beyond
+    // dense up to 12 k unknowns (two n^2 matrices, an n^3 / 3 factorisation per trial), block-sparse beyond; conjugate
+    // gradients on the block-CSR matrix only on request
+    const bool pcg = ctx->linear_solver == SPG_SOLVER_PCG && n > 0;
     const bool sparse = ctx->linear_solver == SPG_SOLVER_SPARSE || (ctx->linear_solver == SPG_SOLVER_AUTO && n > 12000);
-    if (!sparse && n > 32000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_optimize: dense formulation limited to 32k variables (2 x 8 GB)");
+    if (!sparse && !pcg && n > 32000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_optimize: dense formulation limited to 32k variables (2 x 8 GB)");
     DenseStage st;
     if (int rc = stage_global(g, order, fixed_vertices, g->d, st)) return rc;
     spg_optimize_stats os{};
     os.n = n;
-    os.solver = (sparse && n > 0) ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
-    auto *run = os.solver == SPG_SOLVER_SPARSE ? spg::hip_sparse_optimize : spg::hip_dense_optimize;
-    int rc = run(spg::hip_backend_stream(&ctx->be), st.in, (int)n, iterations, os, ctx->err, sizeof ctx->err);
+    os.solver = pcg ? SPG_SOLVER_PCG : (sparse && n > 0) ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
+    ctx->pcg_stats = spg_pcg_stats{};
+    int rc;
+    if (pcg) {
+        spg::bsr::Pattern P;
+        spg::bsr::build_pattern(st.in.nv, st.in.pos, g->d, st.in.ne, st.in.er, st.in.ev, P);
+        const double rel_tol = ctx->pcg_rel_tol > 0 ? ctx->pcg_rel_tol : 1e-10;
+        const int max_iter = ctx->pcg_max_iter > 0 ? ctx->pcg_max_iter : (int)std::min<int64_t>(n, 20000);
+        rc = spg::hip_pcg_optimize(spg::hip_backend_stream(&ctx->be), st.in, P, (int)n, iterations, rel_tol, max_iter, os, ctx->pcg_stats,
+                                   ctx->err, sizeof ctx->err);
+    } else {
+        auto *run = os.solver == SPG_SOLVER_SPARSE ? spg::hip_sparse_optimize : spg::hip_dense_optimize;
+        rc = run(spg::hip_backend_stream(&ctx->be), st.in, (int)n, iterations, os, ctx->err, sizeof ctx->err);
+    }
     // the estimates changed on the device: refresh the host mirror's copies
     if (int rc2 = sync_host(g)) return rc2;
     {

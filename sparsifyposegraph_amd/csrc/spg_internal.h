@@ -115,6 +115,15 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,
                             const int64_t *vpo_base, const int64_t *vpo_other, double *kld, spg_cov_stats &stats, char *err, size_t errlen);
 
+// Block-CSR information, H X and the PCG solver for optimize() (spg_bsr.inc; pattern: spg_bsr_pattern.hpp, host only).
+// in.pos = D * block row of every variable; P is the pattern of that numbering.
+namespace bsr { struct Pattern; }
+int hip_bsr_information(void *stream, const DenseGraphIn &in, const bsr::Pattern &P, double *blocks, char *err, size_t errlen);
+int hip_bsr_apply(void *stream, const DenseGraphIn &in, const bsr::Pattern &P, const double *X, int nrhs, double *Y, char *err, size_t errlen);
+int hip_pcg_optimize(void *stream, const DenseGraphIn &in, const bsr::Pattern &P, int n, int iterations, double rel_tol, int max_iter,
+                     spg_optimize_stats &out, spg_pcg_stats &pcg, char *err, size_t errlen);
+int hip_bsr_bench(void *stream, const DenseGraphIn &in, const bsr::Pattern &P, int reps, double *out, char *err, size_t errlen);
+
 // Interior-point NFR (spg_nfr_ip.hip): blankets of the Dense / Subgraph patterns without a closed form, one workgroup
 // each, everything in a per-blanket slice of a global workspace.
 struct IpArgs {
@@ -152,3 +161,6 @@ void rccl_comm_destroy(void *handle);
 extern "C" int spg_debug_set_stream_port(spg_ctx *ctx, void *stream_port);
 // (tests) one of the device linear-algebra routines of the generic NFR kernel on host arrays; device 0 must be usable
 extern "C" int spg_debug_la(int op, int M, int N, int K, int flags, int mode, double *A, int ra, int lda, double *B, int rb, int ldb, double *C, int rc, int ldc, int *ok);
+// (tools/bsr_bench.py) mean HIP-event ms over `reps` runs: out[0] block-CSR assembly, out[1] one product H x, out[2] assembly
+// into the sparse solver's fronts; out[3] = number of blocks
+extern "C" int spg_debug_bsr_bench(spg_graph *g, int32_t fixed_id, int reps, double *out);

@@ -12,6 +12,9 @@ from .lib import Context, check, load
 
 _f64p, _i32p, _i64p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 
+# Context.set_linear_solver: SOLVER_PCG solves optimize()'s linear systems by preconditioned conjugate gradients
+SOLVER_AUTO, SOLVER_DENSE, SOLVER_SPARSE, SOLVER_PCG = abi.SOLVER_AUTO, abi.SOLVER_DENSE, abi.SOLVER_SPARSE, abi.SOLVER_PCG
+
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
@@ -222,6 +225,37 @@ class GraphWrapperHIP:
         rc = self.L.spg_graph_information(self.h, int(fixed_id), _p(out, C.c_double), out.size)
         check(min(int(rc), 0), self.ctx.h, "information")
         return out
+
+    def sparseInformation(self, fixed_id=-1, values=True):
+        """GraphWrapperG2O::sparseInformation (src/graph_wrapper_g2o.cpp:382-396): information() in block-CSR form at any
+        size. Returns (indptr int64[nb + 1], indices int32[nnzb], blocks float64[nnzb, D, D], ids int32[nb]) — the first
+        three are the arguments of scipy.sparse.bsr_matrix((blocks, indices, indptr)); ids names the block rows. Both
+        triangles are stored, block (u, v) is the transpose of block (v, u) bit for bit. values=False: the pattern only
+        (host work, blocks is None)."""
+        d = self.d
+        nnzb = self.L.spg_graph_sparse_information(self.h, int(fixed_id), None, None, None, 0, None)
+        check(min(int(nnzb), 0), self.ctx.h, "sparseInformation")
+        nb = self.numVertices() - 1
+        indptr, indices = np.zeros(nb + 1, np.int64), np.zeros(max(int(nnzb), 1), np.int32)
+        blocks = np.zeros((max(int(nnzb), 1), d, d)) if values else None
+        ids = np.zeros(max(nb, 1), np.int32)
+        rc = self.L.spg_graph_sparse_information(self.h, int(fixed_id), _p(indptr, C.c_int64), _p(indices, C.c_int32),
+                                                 _p(blocks, C.c_double) if values else None, int(nnzb), _p(ids, C.c_int32))
+        check(min(int(rc), 0), self.ctx.h, "sparseInformation")
+        return indptr, indices[:int(nnzb)], (blocks[:int(nnzb)] if values else None), ids[:nb]
+
+    def informationApply(self, X, fixed_id=-1):
+        """H @ X with H = information(fixed_id), assembled block-CSR on the device and never formed densely. X: float64[n]
+        or float64[nrhs, n] (one vector per row), n = D * (vertices - 1); returns the same shape."""
+        X = np.ascontiguousarray(X, np.float64)
+        n = self.d * (self.numVertices() - 1)
+        if X.ndim not in (1, 2) or X.shape[-1] != n:
+            raise ValueError(f"informationApply: X must be [{n}] or [nrhs, {n}], got {X.shape}")
+        Y = np.zeros_like(X)
+        nrhs = 1 if X.ndim == 1 else X.shape[0]
+        if n > 0 or nrhs <= 0:
+            check(self.L.spg_graph_information_apply(self.h, int(fixed_id), _p(X, C.c_double), nrhs, _p(Y, C.c_double)), self.ctx.h, "informationApply")
+        return Y
 
     def covariance(self, fixed_id=-1):
         """GraphWrapperG2O::covariance (src/graph_wrapper_g2o.cpp:368-373): inverse of information(), dense on

@@ -65,6 +65,8 @@ SYMBOLS = {
     "spg_graph_last_blankets": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i32p, _f64p, _f64p]),
     "spg_graph_substitute_edge": (C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _f64p, _f64p]),
     "spg_graph_information": (C.c_int64, [C.c_void_p, C.c_int32, _f64p, C.c_int64]),
+    "spg_graph_sparse_information": (C.c_int64, [C.c_void_p, C.c_int32, _i64p, _i32p, _f64p, C.c_int64, _i32p]),
+    "spg_graph_information_apply": (C.c_int, [C.c_void_p, C.c_int32, _f64p, C.c_int, _f64p]),
     "spg_graph_kullback_leibler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.KldTerms)]),
     "spg_graph_marginal_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovStats)]),
     "spg_graph_joint_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovStats)]),
@@ -72,6 +74,8 @@ SYMBOLS = {
     "spg_graph_pair_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
     "spg_graph_joint_marginal_covariance": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
+    "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
+    "spg_ctx_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(abi.PcgStats)]),
     "spg_sparse_plan": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.POINTER(abi.SparsePlanInfo),
                                   _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int64]),
     "spg_graph_optimize": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(abi.OptimizeStats)]),
@@ -189,8 +193,20 @@ class Context:
         return self.L.spg_ctx_stream(self.h)
 
     def set_linear_solver(self, solver):
-        """abi.SOLVER_AUTO / SOLVER_DENSE / SOLVER_SPARSE for optimize() and the global KLD of this context's graphs."""
+        """abi.SOLVER_AUTO / SOLVER_DENSE / SOLVER_SPARSE for optimize() and the global KLD of this context's graphs;
+        abi.SOLVER_PCG: optimize() by preconditioned conjugate gradients (the KLD and the covariances treat it as AUTO)."""
         check(self.L.spg_ctx_set_linear_solver(self.h, int(solver)), self.h, "spg_ctx_set_linear_solver")
+
+    def set_pcg(self, rel_tol=0.0, max_iter=0):
+        """spg_ctx_set_pcg: stop PCG at ||r|| <= rel_tol ||b|| or after max_iter iterations; <= 0: the defaults
+        (1e-10, min(n, 20000))."""
+        check(self.L.spg_ctx_set_pcg(self.h, float(rel_tol), int(max_iter)), self.h, "spg_ctx_set_pcg")
+
+    def pcg_stats(self):
+        """spg_ctx_pcg_stats: PCG counters of the context's last optimize call (all zero if it did not run PCG)."""
+        st = abi.PcgStats()
+        check(self.L.spg_ctx_pcg_stats(self.h, C.byref(st)), self.h, "spg_ctx_pcg_stats")
+        return st.asdict()
 
     def synchronize(self):
         check(self.L.spg_ctx_synchronize(self.h), self.h, "spg_ctx_synchronize")
