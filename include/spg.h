@@ -411,7 +411,7 @@ int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, cons
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the
  * smallest id), g2o's Levenberg-Marquardt for up to `iterations` iterations (the reference uses 50),
- * no robust kernel. On the device (Hessian assembly, Cholesky of H + lambda I, triangular solves, pose updates,
+ * plain least squares unless the graph has a robust kernel (spg_graph_set_robust_kernel below). On the device (Hessian assembly, Cholesky of H + lambda I, triangular solves, pose updates,
  * chi2): dense (blocked fp64-MFMA Cholesky) up to 12 k scalar variables, block-sparse multifrontal (nested
  * dissection on the host, fronts on the matrix cores: CHOLMOD's role) beyond — see spg_ctx_set_linear_solver.
  * The estimates of the graph are updated in place. */
@@ -467,6 +467,38 @@ int spg_sparse_plan(int n_blocks, const int32_t *adj_ptr, const int32_t *adj, in
 int spg_graph_optimize_fixed(spg_graph *g, int iterations, const int32_t *fixed_ids, int n_fixed, spg_optimize_stats *out);
 /* _so->chi2(): sum of e^T Omega e over all edges at the current estimates (src/graph_wrapper_g2o.cpp:501,519) */
 int spg_graph_chi2(spg_graph *g, double *chi2);
+
+/* ---- robust kernels for optimize() -----------------------------------------------------------
+ * g2o's OptimizableGraph::Edge::setRobustKernel in its IRLS form, the second-order term left out as g2o leaves it out.
+ * For a binary pose-pose edge with s = e^T Omega e the kernel supplies rho(s) and the weight w = d rho / d s:
+ *   cost = sum rho(s_e),   H = sum w_e J_e^T Omega_e J_e,   b = -sum w_e J_e^T Omega_e e_e.
+ * With width delta > 0:
+ *   SPG_ROBUST_HUBER          rho = s if s <= delta^2, else 2 delta sqrt(s) - delta^2;   w = 1, else delta / sqrt(s)
+ *   SPG_ROBUST_CAUCHY         rho = delta^2 log1p(s / delta^2);                          w = 1 / (1 + s / delta^2)
+ *   SPG_ROBUST_GEMAN_MCCLURE  rho = delta^2 s / (delta^2 + s);                           w = (delta^2 / (delta^2 + s))^2
+ *   SPG_ROBUST_DCS (Phi = delta)  rho = c^2 s + Phi (1 - c)^2, c = min(1, 2 Phi / (Phi + s));   w = c^2
+ * (DCS: w is the derivative with the switch variable c held — dynamic covariance scaling's definition and g2o's weight;
+ * with c substituted rho equals Phi for every s > Phi.)
+ * The kernel applies to the binary edges whose two vertex ids differ by at least min_id_gap (1: every binary edge; 2:
+ * consecutive-id odometry edges are left alone; values <= 0 are treated as 1). GLC edges, MULTI edges and self-loops
+ * always keep w = 1 and rho = s.
+ * The setting belongs to the graph; spg_graph_clone_portion copies it, the .g2o writer does not serialise it.
+ * Honoured by spg_graph_optimize and spg_graph_optimize_fixed on all three solvers: with a kernel set, chi2_initial and
+ * chi2_final of spg_optimize_stats are sum rho, and LM's gain test uses sum rho. NOT honoured — plain least squares
+ * whatever the setting — by spg_graph_chi2, spg_graph_information, _sparse_information, _information_apply,
+ * _covariance and the covariance-block calls, both KLD calls and everything under marginalisation.
+ * Usage: optimise robustly, then clear the kernel (or sparsify, which never sees it) before optimising the sparsified
+ * graph: the new NFR edges are binary and would otherwise be down-weighted like measurements. */
+enum { SPG_ROBUST_NONE = 0, SPG_ROBUST_HUBER = 1, SPG_ROBUST_CAUCHY = 2, SPG_ROBUST_GEMAN_MCCLURE = 3, SPG_ROBUST_DCS = 4 };
+/* Host only, any backend. SPG_EINVAL: unknown kind; delta not finite and > 0 with kind != NONE (NONE ignores delta);
+ * a stepwise marginalisation is active. */
+int spg_graph_set_robust_kernel(spg_graph *g, int kind, double delta, int min_id_gap);
+int spg_graph_get_robust_kernel(const spg_graph *g, int *kind, double *delta, int *min_id_gap);
+/* Per live edge at the stored estimates, in the order of spg_graph_get_edges (the edge order is canonicalised first, as
+ * there): chi2[e] = the plain s, for n-ary edges too; rho[e] and weight[e] follow the graph's kernel (s and 1 without
+ * one, and for the edges it does not apply to). Returns the number of live edges; the arrays (each may be NULL) are
+ * written when cap >= that count. Values need the HIP backend (SPG_ESTATE). */
+int spg_graph_edge_chi2(spg_graph *g, double *chi2, double *rho, double *weight, int cap);
 
 /* ---- round-stepping form of the same call, for multi-GPU sharding ---------------------------
  * All ranks hold a replica and run the same deterministic scheduler; rank r computes its slice of

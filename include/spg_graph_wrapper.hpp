@@ -321,6 +321,26 @@ public:
         return st;
     }
     const spg_optimize_stats &lastOptimize() const { return _last_opt; }
+    // g2o's setRobustKernel for optimize() / chi2(other) (include/spg.h at spg_graph_set_robust_kernel): SPG_ROBUST_* of
+    // width delta on the binary edges whose vertex ids are at least minIdGap apart. chi2(), information(), the covariances,
+    // the KLDs and the marginalisation never see it; clear it (SPG_ROBUST_NONE) before optimising a sparsified graph.
+    void setRobustKernel(int kind, double delta = 1.0, int minIdGap = 1) { check(spg_graph_set_robust_kernel(_g, kind, delta, minIdGap), "setRobustKernel"); }
+    struct RobustKernel { int kind; double delta; int minIdGap; };
+    RobustKernel robustKernel() const {
+        RobustKernel k{};
+        check(spg_graph_get_robust_kernel(_g, &k.kind, &k.delta, &k.minIdGap), "robustKernel");
+        return k;
+    }
+    // per edge, in the order of edges(), at the stored estimates: the plain chi2, and rho / weight of the robust kernel
+    struct EdgeChi2 { std::vector<double> chi2, rho, weight; };
+    EdgeChi2 edgeChi2() const {
+        EdgeChi2 out;
+        const int n = spg_graph_edge_chi2(_g, nullptr, nullptr, nullptr, 0);
+        check(std::min(n, 0), "edgeChi2");
+        out.chi2.resize((size_t)n); out.rho.resize((size_t)n); out.weight.resize((size_t)n);
+        check(std::min(spg_graph_edge_chi2(_g, out.chi2.data(), out.rho.data(), out.weight.data(), n), 0), "edgeChi2");
+        return out;
+    }
     // GraphWrapperG2O::clonePortion (src/graph_wrapper_g2o.cpp:334-356): vertices / edges up to maxid, optimised
     GraphWrapperHIP *clonePortion(int maxid) override {
         spg_graph *c = nullptr;

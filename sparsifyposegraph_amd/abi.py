@@ -114,6 +114,8 @@ class SparsePlanInfo(C.Structure):
 
 
 SOLVER_AUTO, SOLVER_DENSE, SOLVER_SPARSE, SOLVER_PCG = 0, 1, 2, 3
+# SPG_ROBUST_* (include/spg.h): robust kernel of optimize(), spg_graph_set_robust_kernel
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_GEMAN_MCCLURE, ROBUST_DCS = 0, 1, 2, 3, 4
 
 
 class PcgStats(C.Structure):

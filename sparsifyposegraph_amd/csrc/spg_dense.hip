@@ -479,6 +479,7 @@ struct GraphDev {
     const int64_t *aw_off;    // per edge: offset of its weighted Jacobian in aw (GLC edges), -1 otherwise
     double *aw;
     int nv, ne;
+    const double *ew = nullptr;   // per edge: robust weight of a binary edge's information (lm_run with a kernel set), nullptr = none
 };
 
 template <int D>
@@ -628,7 +629,9 @@ __global__ __launch_bounds__(64) void dense_assemble_kernel(GraphDev g, Sink sin
             }
             if (act) {
                 int lo = r < c ? r : c, hi = r < c ? c : r;
-                Om[tid] = rec[PS + lo * D - lo * (lo - 1) / 2 + (hi - lo)];
+                double om = rec[PS + lo * D - lo * (lo - 1) / 2 + (hi - lo)];
+                if (g.ew) om = g.ew[e] * om;   // IRLS: w Omega weights H and b alike
+                Om[tid] = om;
             }
             __syncthreads();
             if (act) {
@@ -708,6 +711,66 @@ __global__ void edge_chi2_kernel(GraphDev g, double *chi) {
         for (int p = 0; p < rr; p++) s += wr[p] * wr[p];
     }
     chi[e] = s;
+}
+
+// Robust kernels of include/spg.h (SPG_ROBUST_*) on s = e^T Omega e >= 0, width delta > 0: rho(s) and the weight w
+// (d rho / d s; DCS: with its switch variable c held).
+// No division by s: Huber's w = delta / sqrt(s) is only taken for s > delta^2 > 0.
+__device__ __forceinline__ void robust_rho_w(int kind, double delta, double s, double &rho, double &w) {
+    const double d2 = delta * delta;
+    rho = s; w = 1.0;
+    if (kind == SPG_ROBUST_HUBER) {
+        if (s > d2) { const double r = sqrt(s); rho = 2.0 * delta * r - d2; w = delta / r; }
+    } else if (kind == SPG_ROBUST_CAUCHY) {
+        const double t = s / d2;
+        rho = d2 * log1p(t); w = 1.0 / (1.0 + t);
+    } else if (kind == SPG_ROBUST_GEMAN_MCCLURE) {
+        const double a = d2 / (d2 + s);
+        rho = a * s; w = a * a;
+    } else if (kind == SPG_ROBUST_DCS) {
+        const double c = fmin(1.0, 2.0 * delta / (delta + s)), u = 1.0 - c;
+        rho = c * c * s + delta * u * u; w = c * c;
+    }
+}
+
+// Per live edge, one lane each: s (binary: e^T Omega e from the error alone; n-ary: ||W e||^2 from
+// glc_weighted_jacobian_kernel), rho(s) and the weight w. elig[e] != 0: the graph's kernel applies to the edge (staged by
+// the host: a binary edge between two different vertices whose ids are at least min_id_gap apart); every other edge
+// reports (s, s, 1). Each output may be nullptr.
+template <int D>
+__global__ __launch_bounds__(64) void edge_robust_kernel(GraphDev g, const uint8_t *elig, int kind, double delta, double *chi, double *rho_out, double *w_out) {
+    constexpr int PS = (D == 6) ? 7 : 3, PSZ = (D == 6) ? kIso : 3;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= g.ne) return;
+    const spg_edge_ref er = g.er[e];
+    double s = 0;
+    if (er.kind == SPG_EDGE_BINARY) {
+        const double *rec = g.arena + er.off;
+        double Xi[PSZ], Xj[PSZ], err[D];
+        load_pose<D>(g.arena, g.vpo[g.ev[er.vbegin]], Xi);
+        load_pose<D>(g.arena, g.vpo[g.ev[er.vbegin + 1]], Xj);
+        if (D == 6) {
+            double Z[kIso];
+            iso_from_tq(rec, Z);
+            se3_edge_err(Xi, Xj, Z, err);
+        } else {
+            se2_edge_err(Xi, Xj, rec, err);
+        }
+        int p = PS;
+#pragma unroll
+        for (int i = 0; i < D; i++)
+#pragma unroll
+            for (int j = i; j < D; j++) { s += ((i == j) ? 1.0 : 2.0) * err[i] * rec[p] * err[j]; p++; }
+    } else {
+        const int dq = D * er.nv, rr = nary_rows(er, g.arena, D);
+        const double *wr = g.aw + g.aw_off[e] + (int64_t)rr * dq;
+        for (int p = 0; p < rr; p++) s += wr[p] * wr[p];
+    }
+    double rho = s, w = 1.0;
+    if (elig[e]) robust_rho_w(kind, delta, s, rho, w);
+    if (chi) chi[e] = s;
+    if (rho_out) rho_out[e] = rho;
+    if (w_out) w_out[e] = w;
 }
 
 // out[slot] = sum v[0..n) in a fixed order (one workgroup)
@@ -1681,6 +1744,9 @@ int hip_dense_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &ot
 // restored; stop after 10 failed trials, rho == 0 or a non-finite lambda. The host sees four scalars
 // per trial. The linear algebra behind it is either dense (DenseLM below) or the block-sparse multifrontal
 // solver of spg_sparse.inc (SparseLM).
+// With a robust kernel staged (in.robust_kind) this is g2o's IRLS: every iteration takes the weights w_e at its estimates
+// (edge_robust_kernel), the assembly scales the informations of the eligible binary edges by them, and chi2 — the gain
+// test's and the stats' — is sum rho. Without one the launch sequence is what it was before the kernels existed.
 }  // namespace spg
 
 namespace {
@@ -1704,21 +1770,37 @@ int lm_run(hipStream_t s, const spg::DenseGraphIn &in, GraphBufs &gb, int n, int
     HIPCHK(hipMalloc(&chi.p, (size_t)std::max(in.ne, 1) * 8));
     HIPCHK(hipMalloc(&scal.p, 4 * 8));
     HIPCHK(hipMalloc(&backup.p, (size_t)std::max(in.nv, 1) * PS * 8));
+    // robust kernel (include/spg.h at spg_graph_set_robust_kernel): per-edge weights for the assembly, rho for the cost
+    const bool robust = in.robust_kind != SPG_ROBUST_NONE && in.ne > 0;
+    DevBuf elig, ew;
+    if (robust) {
+        if (int rc = upload(elig, in.robust_elig, (size_t)in.ne, s)) return rc;
+        HIPCHK(hipMalloc(&ew.p, (size_t)in.ne * 8));
+    }
     EventTimer timer;
     HIPCHK(timer.start(s));
     double *arena = (double *)const_cast<void *>(in.dev_arena);
+    // rho per edge into chi and, if asked for, the weights into ew (the n-ary edges' weighted errors must be current)
+    auto robust_edges = [&](bool weights) {
+        by_dim(D, [&](auto d) {
+            hipLaunchKernelGGL((edge_robust_kernel<decltype(d)::value>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (const uint8_t *)elig.p,
+                               in.robust_kind, in.robust_delta, (double *)nullptr, (double *)chi.p, weights ? (double *)ew.p : (double *)nullptr);
+        });
+    };
     auto poses = [&](int mode) {
         by_dim(D, [&](auto d) {
             hipLaunchKernelGGL((pose_update_kernel<decltype(d)::value>), dim3((in.nv + 63) / 64), dim3(64), 0, s, arena, gb.dev.vpo, gb.dev.pos, in.nv, (const double *)sol.p, (double *)backup.p, mode);
         });
     };
     // chi2 of the current estimates into scal[slot] (the GLC kernel refreshes the weighted errors)
+    auto sum_chi_into = [&](int slot) { hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)chi.p, in.ne, (double *)scal.p, slot); };
     auto chi2_into = [&](int slot, bool refresh_glc) {
         by_dim(D, [&](auto d) {
             if (refresh_glc) launch_glc_jacobians<decltype(d)::value>(gb, s);
-            if (in.ne > 0) hipLaunchKernelGGL((edge_chi2_kernel<decltype(d)::value>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (double *)chi.p);
+            if (robust) robust_edges(false);
+            else if (in.ne > 0) hipLaunchKernelGGL((edge_chi2_kernel<decltype(d)::value>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (double *)chi.p);
         });
-        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)chi.p, in.ne, (double *)scal.p, slot);
+        sum_chi_into(slot);
     };
     double h_s[4] = {0, 0, 0, 0};
     double lambda = 0, ni = 2, chi_first = 0, chi_last = 0;
@@ -1727,8 +1809,15 @@ int lm_run(hipStream_t s, const spg::DenseGraphIn &in, GraphBufs &gb, int n, int
     for (; it < iterations && !terminate; it++) {
         // buildSystem: H, b and chi2 at the current estimates
         HIPCHK(hipMemsetAsync(b.p, 0, (size_t)nvec * 8, s));
+        if (robust) {
+            // the weights at the current estimates, before the assembly reads them; the same pass leaves rho in chi
+            by_dim(D, [&](auto d) { launch_glc_jacobians<decltype(d)::value>(gb, s); });
+            robust_edges(true);
+            gb.dev.ew = (const double *)ew.p;
+        }
         if (int rc = lin.build(s, gb, (double *)b.p, (double *)scal.p, err, errlen)) return rc;
-        chi2_into(0, false);
+        if (robust) sum_chi_into(0);   // rho of the pass above: the estimates have not moved
+        else chi2_into(0, false);
         HIPCHK(hipMemcpyAsync(h_s, scal.p, 2 * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         double currentChi = h_s[0];
@@ -1830,6 +1919,34 @@ int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iteratio
     if (rc) return rc;
     if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for the optimiser failed (%d)", rc); return rc; }
     return lm_run(s, in, gb, n, lin.N, iterations, lin, out, err, errlen);
+}
+
+
+int hip_edge_chi2(void *stream, const DenseGraphIn &in, double *chi2, double *rho, double *weight, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    if (in.ne <= 0) return 0;
+    GraphBufs gb;
+    int rc;
+    if ((rc = stage_graph(in, gb, s))) { snprintf(err, errlen, "staging the graph for the per-edge chi2 failed (%d)", rc); return rc; }
+    const bool robust = in.robust_kind != SPG_ROBUST_NONE;
+    const size_t ne = (size_t)in.ne;
+    std::vector<uint8_t> none;
+    if (!robust) none.assign(ne, 0);
+    DevBuf elig, vals;
+    if ((rc = upload(elig, robust ? in.robust_elig : none.data(), ne, s))) return rc;
+    HIPCHK(hipMalloc(&vals.p, 3 * ne * 8));
+    double *d = (double *)vals.p;
+    by_dim(in.D, [&](auto dd) {
+        launch_glc_jacobians<decltype(dd)::value>(gb, s);
+        hipLaunchKernelGGL((edge_robust_kernel<decltype(dd)::value>), dim3((in.ne + 63) / 64), dim3(64), 0, s, gb.dev, (const uint8_t *)elig.p,
+                           in.robust_kind, in.robust_delta, d, d + ne, d + 2 * ne);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (chi2) HIPCHK(hipMemcpy(chi2, d, ne * 8, hipMemcpyDeviceToHost));
+    if (rho) HIPCHK(hipMemcpy(rho, d + ne, ne * 8, hipMemcpyDeviceToHost));
+    if (weight) HIPCHK(hipMemcpy(weight, d + 2 * ne, ne * 8, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // namespace spg

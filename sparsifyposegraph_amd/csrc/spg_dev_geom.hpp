@@ -203,6 +203,15 @@ __device__ __forceinline__ void se3_edge_jac(const double *Xi, const double *Xj,
     }
 }
 
+// The error of se3_edge_jac alone (the same expressions), for callers that need no Jacobian
+__device__ __forceinline__ void se3_edge_err(const double *Xi, const double *Xj, const double *Z, double *err) {
+    double B[kIso], E[kIso], q[4];
+    iso_inv_mul(Xi, Xj, B);   // B = Xi^-1 Xj
+    iso_inv_mul(Z, B, E);     // E = Z^-1 B
+    R_to_quat(E, q);
+    err[0] = E[9]; err[1] = E[10]; err[2] = E[11]; err[3] = q[0]; err[4] = q[1]; err[5] = q[2];
+}
+
 // ------------------------------------------------------------------------------------------ SE2
 __device__ __forceinline__ double normalize_theta(double th) {
     const double PI = 3.14159265358979323846;
@@ -236,6 +245,15 @@ __device__ __forceinline__ void se2_edge_jac(const double *xi, const double *xj,
     Jj[0] = ci;  Jj[1] = si;  Jj[2] = 0;
     Jj[3] = -si; Jj[4] = ci;  Jj[5] = 0;
     Jj[6] = 0;   Jj[7] = 0;   Jj[8] = 1;
+}
+
+// The error of se2_edge_jac alone (the same expressions), for callers that need no Jacobian
+__device__ __forceinline__ void se2_edge_err(const double *xi, const double *xj, const double *z, double *err) {
+    double si = sin(xi[2]), ci = cos(xi[2]);
+    double dx = xj[0] - xi[0], dy = xj[1] - xi[1];
+    err[0] = ci * dx + si * dy - z[0];
+    err[1] = -si * dx + ci * dy - z[1];
+    err[2] = normalize_theta(normalize_theta(xj[2] - xi[2]) - z[2]);
 }
 
 }  // namespace spgdev

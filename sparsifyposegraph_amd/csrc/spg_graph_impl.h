@@ -314,6 +314,10 @@ struct spg_graph {
     bool layout_diverged = false;                     // the graph has streamed on one of several ranks: its arena layout is rank-specific, never shard it again
     int stream_emulation = -1;                        // tests (spg_graph_set_stream_emulation): >= 0 = completion-order seed
     int stream_disabled = 0;                          // SPG_STREAM=0 or spg_graph_set_stream_emulation(g, -2)
+    // robust kernel of spg_graph_optimize / _optimize_fixed (spg_graph_set_robust_kernel): SPG_ROBUST_*, width, and the
+    // smallest vertex-id distance of the binary edges it applies to
+    int robust_kind = 0, robust_gap = 1;
+    double robust_delta = 1.0;
 };
 
 static inline const int32_t *edge_verts(const spg_graph *g, const GEdge &e) {

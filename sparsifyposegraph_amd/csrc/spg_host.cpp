@@ -726,6 +726,7 @@ extern "C" int spg_graph_clone_portion(spg_graph *g, int maxid, spg_graph **out)
         else { int n = g->d * e.nv; rc = spg_graph_add_glc_edge(c, e.nv, ids.data(), (e.len - n) / n, rec, rec + n); }
     }
     if (rc) { spg_graph_destroy(c); return rc; }
+    c->robust_kind = g->robust_kind; c->robust_delta = g->robust_delta; c->robust_gap = g->robust_gap;
     *out = c;
     return 0;
 }

@@ -1,5 +1,5 @@
 // csrc/spg_host_global.cpp — the entry points of include/spg.h that work on a whole graph at once (global KLD,
-// information (dense and block-CSR) and its product, covariance and its blocks, optimize / chi2, the symbolic plan): the graph is staged on the host as one
+// information (dense and block-CSR) and its product, covariance and its blocks, optimize / chi2, the robust kernel and the per-edge chi2, the symbolic plan): the graph is staged on the host as one
 // DenseGraphIn and handed to the device drivers of spg_dense.hip / spg_sparse.inc. Nothing here touches the scheduler.
 #include "spg_graph_impl.h"
 #include "spg_sparse_plan.hpp"
@@ -459,8 +459,58 @@ extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fix
     return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_joint_marginal_covariance");
 }
 
+// ================================================================================= robust kernel
+namespace {
+// The graph's kernel into a staged graph: kind, width and, per live edge in the stage's order, whether it applies — a
+// binary edge between two different vertices whose ids are at least robust_gap apart. `elig` must outlive st.in.
+void stage_robust(const spg_graph *g, DenseStage &st, std::vector<uint8_t> &elig) {
+    if (g->robust_kind == SPG_ROBUST_NONE) return;
+    elig.assign(st.er.size(), 0);
+    for (size_t e = 0; e < st.er.size(); e++) {
+        if (st.er[e].kind != SPG_EDGE_BINARY) continue;
+        const int32_t vi = st.ev[st.er[e].vbegin], vj = st.ev[st.er[e].vbegin + 1];
+        const int64_t gap = std::llabs((int64_t)g->vid[vi] - (int64_t)g->vid[vj]);
+        elig[e] = vi != vj && gap >= g->robust_gap;
+    }
+    st.in.robust_kind = g->robust_kind; st.in.robust_delta = g->robust_delta; st.in.robust_elig = elig.data();
+}
+}  // namespace
+
+extern "C" int spg_graph_set_robust_kernel(spg_graph *g, int kind, double delta, int min_id_gap) {
+    if (!g || g->active || kind < SPG_ROBUST_NONE || kind > SPG_ROBUST_DCS) return SPG_EINVAL;
+    if (kind != SPG_ROBUST_NONE && !(std::isfinite(delta) && delta > 0)) return SPG_EINVAL;
+    g->robust_kind = kind;
+    if (kind != SPG_ROBUST_NONE) g->robust_delta = delta;
+    g->robust_gap = std::max(min_id_gap, 1);
+    return 0;
+}
+
+extern "C" int spg_graph_get_robust_kernel(const spg_graph *g, int *kind, double *delta, int *min_id_gap) {
+    if (!g) return SPG_EINVAL;
+    if (kind) *kind = g->robust_kind;
+    if (delta) *delta = g->robust_delta;
+    if (min_id_gap) *min_id_gap = g->robust_gap;
+    return 0;
+}
+
+extern "C" int spg_graph_edge_chi2(spg_graph *g, double *chi2, double *rho, double *weight, int cap) {
+    if (!g || g->active) return SPG_EINVAL;
+    const int ne = g->n_live_e;
+    if (cap < ne || !(chi2 || rho || weight)) return ne;
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_edge_chi2 needs the HIP backend");
+    if (ne == 0) return 0;
+    // nothing is a variable: only the errors are evaluated. The stage lists the live edges in spg_graph_get_edges order.
+    DenseStage st;
+    if (int rc = stage_global(g, {}, {}, g->d, st)) return rc;
+    std::vector<uint8_t> elig;
+    stage_robust(g, st, elig);
+    int rc = spg::hip_edge_chi2(spg::hip_backend_stream(&g->ctx->be), st.in, chi2, rho, weight, g->ctx->err, sizeof g->ctx->err);
+    return rc ? rc : ne;
+}
+
 // ================================================================================= optimize() (8f.1)
-static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<int32_t> &fixed_vertices, spg_optimize_stats *out) {
+// robust: honour the graph's kernel (spg_graph_chi2 does not)
+static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<int32_t> &fixed_vertices, spg_optimize_stats *out, bool robust = true) {
     spg_ctx *ctx = g->ctx;
     std::vector<int32_t> order = live_vertices_by_id(g);
     std::vector<uint8_t> is_fixed(g->vid.size(), 0);
@@ -474,6 +524,8 @@ static int optimize_with_fixed(spg_graph *g, int iterations, const std::vector<i
     if (!sparse && !pcg && n > 32000) return set_err(ctx, SPG_ECAPACITY, "spg_graph_optimize: dense formulation limited to 32k variables (2 x 8 GB)");
     DenseStage st;
     if (int rc = stage_global(g, order, fixed_vertices, g->d, st)) return rc;
+    std::vector<uint8_t> elig;
+    if (robust) stage_robust(g, st, elig);
     spg_optimize_stats os{};
     os.n = n;
     os.solver = pcg ? SPG_SOLVER_PCG : (sparse && n > 0) ? SPG_SOLVER_SPARSE : SPG_SOLVER_DENSE;
@@ -566,7 +618,7 @@ extern "C" int spg_graph_chi2(spg_graph *g, double *chi2) {
     for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) all.push_back((int32_t)i);
     if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_chi2 needs the HIP backend");
     spg_optimize_stats st{};
-    int rc = optimize_with_fixed(g, 1, all, &st);
+    int rc = optimize_with_fixed(g, 1, all, &st, false);
     if (rc) return rc;
     *chi2 = st.chi2_initial;
     return 0;

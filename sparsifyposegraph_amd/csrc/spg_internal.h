@@ -77,6 +77,11 @@ struct DenseGraphIn {
     const int32_t *ev = nullptr;        // vertex indices of the edges
     int64_t n_ev = 0;
     const void *dev_arena = nullptr;    // device arena of the graph
+    // robust kernel of the graph (SPG_ROBUST_*), honoured by the three optimize drivers only; robust_elig[e] != 0: it
+    // applies to live edge e (built by the host from the vertex ids)
+    int robust_kind = 0;
+    double robust_delta = 0;
+    const uint8_t *robust_elig = nullptr;   // [ne] when robust_kind != 0
 };
 // Results of the global-path drivers below land in the public structs of include/spg.h. One rule for all of them: a
 // driver ADDS to the counters and seconds of the struct it is handed (the marginal KLD runs two factorisations into one)
@@ -95,6 +100,9 @@ int hip_la_test(int op, int M, int N, int K, int flags, int mode, double *A, int
 // frees the scratch the large-blanket pipeline keeps between calls (device block + pinned staging); called when a backend goes
 void hip_big_release_scratch();
 int hip_dense_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen);
+// Per live edge at the stored estimates: s = chi2 of the edge, rho(s) and the weight of the graph's robust kernel (in.robust_*;
+// no kernel: rho = s, w = 1). Host arrays of in.ne doubles, each may be nullptr (spg_dense.hip: edge_robust_kernel).
+int hip_edge_chi2(void *stream, const DenseGraphIn &in, double *chi2, double *rho, double *weight, char *err, size_t errlen);
 
 // Block-sparse multifrontal path of the same two calls (spg_sparse.inc, symbolic phase in spg_sparse_plan.hpp).
 int hip_sparse_optimize(void *stream, const DenseGraphIn &in, int n, int iterations, spg_optimize_stats &out, char *err, size_t errlen);

@@ -216,6 +216,28 @@ class GraphWrapperHIP:
                 self.setEstimate(int(i), p)
         return st.chi2_final
 
+    def setRobustKernel(self, kind, delta=1.0, minIdGap=1):
+        """g2o's setRobustKernel for the binary edges whose vertex ids are at least minIdGap apart (2 leaves
+        consecutive-id odometry alone): abi.ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE / DCS of width delta. optimize()
+        and chi2(other) honour it (their chi2 is then sum rho); chi2(), information(), the covariances, the KLDs and the
+        marginalisation never do. Clear it (ROBUST_NONE) before optimising a sparsified graph."""
+        check(self.L.spg_graph_set_robust_kernel(self.h, int(kind), float(delta), int(minIdGap)), self.ctx.h, "setRobustKernel")
+
+    def robustKernel(self):
+        """(kind, delta, minIdGap) as set by setRobustKernel"""
+        k, g, d = C.c_int(), C.c_int(), C.c_double()
+        check(self.L.spg_graph_get_robust_kernel(self.h, C.byref(k), C.byref(d), C.byref(g)), self.ctx.h, "robustKernel")
+        return k.value, d.value, g.value
+
+    def edgeChi2(self):
+        """Per edge, in the order of edges(), at the stored estimates: (chi2, rho, weight) — the plain e^T Omega e (n-ary
+        edges: ||W e||^2), and rho / weight of the graph's robust kernel (chi2 and 1 without one and for exempt edges)."""
+        n = self.L.spg_graph_edge_chi2(self.h, None, None, None, 0)
+        check(n, self.ctx.h, "edgeChi2")
+        s, rho, w = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        check(self.L.spg_graph_edge_chi2(self.h, _p(s, C.c_double), _p(rho, C.c_double), _p(w, C.c_double), n), self.ctx.h, "edgeChi2")
+        return s[:n], rho[:n], w[:n]
+
     def information(self, fixed_id=-1):
         """GraphWrapperG2O::information (src/graph_wrapper_g2o.cpp:351-358): dense Gauss-Newton
         information at the stored estimates, all vertices but the fixed one (default: smallest id)."""
