@@ -468,6 +468,58 @@ int spg_graph_optimize_fixed(spg_graph *g, int iterations, const int32_t *fixed_
 /* _so->chi2(): sum of e^T Omega e over all edges at the current estimates (src/graph_wrapper_g2o.cpp:501,519) */
 int spg_graph_chi2(spg_graph *g, double *chi2);
 
+/* ---- initialize(): initial pose estimates from the measurements ------------------------------
+ * optimize() starts from the stored estimates; this call produces them. The fixed vertex (fixed_id < 0: the smallest
+ * live id) keeps its stored pose, which defines the gauge; every other live vertex's estimate is overwritten, on the
+ * host and on the device, the way optimize() leaves them (SE3 quaternions unit length with w >= 0, SE2 angles in
+ * (-pi, pi]). The result is a function of the measurements, the informations and the fixed pose alone: the stored
+ * estimates of the other vertices are never read. Only binary pose-pose edges enter (parallel ones all do); GLC edges,
+ * MULTI edges and self-loops are ignored and counted; the robust kernel is ignored.
+ *
+ * SPG_INIT_SPANNING_TREE (host, any backend) — g2o's computeInitialGuess with unit edge costs: breadth-first search from
+ * the fixed vertex over the binary edges. The parent of a vertex is its neighbour in the previous level with the
+ * smallest id; among parallel edges to it the one that comes first in the order of spg_graph_get_edges (the edge order
+ * is canonicalised first, as there). Along the edge T_child = T_parent Z, against it T_child = T_parent Z^-1.
+ *
+ * SPG_INIT_CHORDAL (device; SPG_ESTATE without the HIP backend) — chordal relaxation (Carlone et al. 2015, GTSAM's
+ * InitializePose3) with scalar weights. Edge e = (a, b), Z_e = T_a^-1 T_b = (R_ab, t_ab), information Omega_e with the
+ * translation block first. Weights: kappa_e = Omega_theta_theta (SE2) or trace(Omega[3:6,3:6]) / 3 (SE3);
+ * tau_e = trace(Omega_tt) / 2 (SE2) or / 3 (SE3). An edge with a weight that is not finite and > 0 is SPG_EINVAL.
+ *   1. rotations: SE3 unknowns M_i = R_i^T, minimise sum kappa_e ||M_b - R_ab^T M_a||_F^2 with M_f fixed (three
+ *      independent columns); SE2 unknowns m_i = (cos theta_i, sin theta_i), minimise sum kappa_e ||m_b - Rot(theta_ab) m_a||^2.
+ *      Normal equations over the free vertices: diagonal blocks (sum kappa_e) I, block (b, a) -= kappa_e R_ab^T, block
+ *      (a, b) -= kappa_e R_ab, the fixed vertex's terms on the right-hand side.
+ *   2. projection: SE3 R_i^T = U diag(1, 1, det(U V^T)) V^T of M_i = U S V^T; SE2 theta_i = atan2(m_1, m_0). A vertex is
+ *      degenerate when ||m_i|| < 1e-6 (SE2) or the second-largest singular value of M_i is below 1e-6 (SE3): it takes
+ *      the orientation of the spanning tree above and is counted. (With one fixed vertex and rotation measurements that
+ *      disagree around cycles, the relaxed blocks shrink with the distance from the fixed vertex: on graphs hundreds of
+ *      loops deep with large rotation noise most vertices can end below this threshold. Read `degenerate`.)
+ *   3. translations: minimise sum tau_e ||t_b - t_a - R_a t_ab||^2 with t_f fixed and the rotations of step 2 — the
+ *      tau-weighted graph Laplacian (x) I.
+ * Both systems are factorised by the block-sparse multifrontal Cholesky over one nested-dissection plan with 3 x 3
+ * blocks (SE2 is embedded: Rz blocks, zero third component). spg_ctx_set_linear_solver does not apply: there is no
+ * dense and no PCG route, SPG_SOLVER_PCG and every other setting behave as AUTO, as for the covariance calls. The only
+ * size limit is free device memory (SPG_ECAPACITY). A failed factorisation is SPG_ENOTPD (it cannot occur on a
+ * connected graph with positive weights).
+ *
+ * Errors, all found before anything is computed, and the graph is unchanged after any error: SPG_EINVAL for an unknown
+ * method, an unknown fixed_id, an active stepwise marginalisation, a live vertex that no chain of binary edges joins to
+ * the fixed one (the message names the smallest such id), a bad weight (chordal). A graph that holds only the fixed
+ * vertex is a successful no-op. */
+enum { SPG_INIT_SPANNING_TREE = 0, SPG_INIT_CHORDAL = 1 };
+typedef struct {
+    int32_t method;            /* what ran */
+    int32_t n_vertices;        /* live vertices, the fixed one included */
+    int32_t edges_used;        /* binary edges that entered (self-loops excluded) */
+    int32_t edges_ignored;     /* GLC, MULTI and self-loop edges */
+    int32_t tree_depth;        /* deepest BFS level of the spanning tree */
+    int32_t degenerate;        /* chordal: vertices whose relaxed rotation could not be projected */
+    double chi2_before, chi2_after;   /* spg_graph_chi2 before / after; NaN on a backend without HIP */
+    double device_seconds;     /* HIP-event time of assembly + factorisations + solves + projection (0 for the tree) */
+    int32_t supernodes; double front_bytes, factor_flops;   /* as in spg_optimize_stats */
+} spg_init_stats;
+int spg_graph_initialize(spg_graph *g, int method, int32_t fixed_id, spg_init_stats *out /* may be NULL */);
+
 /* ---- robust kernels for optimize() -----------------------------------------------------------
  * g2o's OptimizableGraph::Edge::setRobustKernel in its IRLS form, the second-order term left out as g2o leaves it out.
  * For a binary pose-pose edge with s = e^T Omega e the kernel supplies rho(s) and the weight w = d rho / d s:

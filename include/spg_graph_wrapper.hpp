@@ -321,6 +321,15 @@ public:
         return st;
     }
     const spg_optimize_stats &lastOptimize() const { return _last_opt; }
+    // Initial estimates from the measurements alone, the step before optimize() for a graph with poor stored poses
+    // (include/spg.h at spg_graph_initialize): SPG_INIT_CHORDAL on the device, SPG_INIT_SPANNING_TREE on the host (g2o's
+    // computeInitialGuess). The fixed vertex (fixed_id < 0: the smallest id) keeps its pose.
+    spg_init_stats initialize(int method = SPG_INIT_CHORDAL, int fixed_id = -1) {
+        spg_init_stats st;
+        drop_views();
+        check(spg_graph_initialize(_g, method, fixed_id, &st), "initialize");
+        return st;
+    }
     // g2o's setRobustKernel for optimize() / chi2(other) (include/spg.h at spg_graph_set_robust_kernel): SPG_ROBUST_* of
     // width delta on the binary edges whose vertex ids are at least minIdGap apart. chi2(), information(), the covariances,
     // the KLDs and the marginalisation never see it; clear it (SPG_ROBUST_NONE) before optimising a sparsified graph.

@@ -107,6 +107,20 @@ class OptimizeStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# SPG_INIT_* (include/spg.h): method of spg_graph_initialize
+INIT_SPANNING_TREE, INIT_CHORDAL = 0, 1
+
+
+class InitStats(C.Structure):
+    """spg_init_stats (include/spg.h)"""
+    _fields_ = [("method", C.c_int32), ("n_vertices", C.c_int32), ("edges_used", C.c_int32), ("edges_ignored", C.c_int32),
+                ("tree_depth", C.c_int32), ("degenerate", C.c_int32), ("chi2_before", C.c_double), ("chi2_after", C.c_double),
+                ("device_seconds", C.c_double), ("supernodes", C.c_int32), ("front_bytes", C.c_double), ("factor_flops", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SparsePlanInfo(C.Structure):
     """spg_sparse_plan_info (include/spg.h)"""
     _fields_ = [("n_supernodes", C.c_int32), ("n_marg_supernodes", C.c_int32), ("n_levels", C.c_int32), ("pad_", C.c_int32),

@@ -1953,3 +1953,4 @@ int hip_edge_chi2(void *stream, const DenseGraphIn &in, double *chi2, double *rh
 
 #include "spg_sparse.inc"
 #include "spg_bsr.inc"
+#include "spg_init.inc"

@@ -339,6 +339,9 @@ void canonicalize_edge_order(spg_graph *g);
 #pragma GCC visibility push(hidden)
 int arena_ensure(spg_graph *g, int64_t need);
 int add_edge_idx(spg_graph *g, int kind, int nv, const int32_t *vix, int64_t off, int32_t len, int64_t key = -1);
+// poses in arena layout (SE2: x y theta in [-pi, pi); SE3: t, unit quaternion x y z w)
+void pose_compose(int d, const double *a, const double *b, double *o);   // o = a * b (o may alias neither)
+void pose_inverse(int d, const double *a, double *o);
 // spg_host_rounds.cpp
 void quiesce_submission(spg_graph *g);   // wait until the submission thread has handed over every batch in its queue
 // spg_host_stream.cpp

@@ -908,6 +908,8 @@ double wrap_theta(double th) {
     if (m < -PI) m += 2 * PI;
     return m;
 }
+}  // namespace
+// (the two below also serve the spanning tree of spg_graph_initialize, spg_host_global.cpp: declared in spg_graph_impl.h)
 void pose_compose(int d, const double *a, const double *b, double *o) {  // o = a * b (o may alias neither)
     if (d == 3) {
         double c = std::cos(a[2]), s = std::sin(a[2]);
@@ -932,6 +934,7 @@ void pose_inverse(int d, const double *a, double *o) {
         o[3] = qi[0]; o[4] = qi[1]; o[5] = qi[2]; o[6] = qi[3];
     }
 }
+namespace {
 bool dense_inverse(int n, std::vector<double> &A) {  // Gauss-Jordan, partial pivoting (Eigen .inverse())
     std::vector<double> X((size_t)n * n, 0.0);
     for (int i = 0; i < n; i++) X[(size_t)i * n + i] = 1.0;

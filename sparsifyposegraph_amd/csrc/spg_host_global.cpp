@@ -611,15 +611,134 @@ extern "C" int spg_graph_optimize_fixed(spg_graph *g, int iterations, const int3
     return optimize_with_fixed(g, iterations, fx, out);
 }
 
-extern "C" int spg_graph_chi2(spg_graph *g, double *chi2) {
-    if (!g || !chi2 || g->active) return SPG_EINVAL;
-    // zero iterations with every vertex fixed: the optimiser's entry evaluates chi2 and returns
+// zero iterations with every vertex fixed: the optimiser's entry evaluates chi2 and returns
+static int graph_chi2(spg_graph *g, double *chi2) {
     std::vector<int32_t> all;
     for (size_t i = 0; i < g->vid.size(); i++) if (g->valive[i]) all.push_back((int32_t)i);
-    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_chi2 needs the HIP backend");
     spg_optimize_stats st{};
     int rc = optimize_with_fixed(g, 1, all, &st, false);
     if (rc) return rc;
     *chi2 = st.chi2_initial;
+    return 0;
+}
+
+extern "C" int spg_graph_chi2(spg_graph *g, double *chi2) {
+    if (!g || !chi2 || g->active) return SPG_EINVAL;
+    if (!g->ctx->is_hip) return set_err(g->ctx, SPG_ESTATE, "spg_graph_chi2 needs the HIP backend");
+    return graph_chi2(g, chi2);
+}
+
+// ================================================================================= initialize()
+namespace {
+// Breadth-first spanning tree over the binary edges from `fixed` (spg_graph_initialize in include/spg.h states the
+// tie-breaks): level[v] (-1 = not reached), and tree = the composed pose of every reached vertex, indexed by vertex
+// (pose stride apart), the fixed one's taken from the host mirror. Counts the edges that enter and those that do not.
+struct SpanningTree {
+    std::vector<int32_t> level;
+    std::vector<double> tree;
+    int depth = 0, used = 0, ignored = 0;
+};
+bool enters_initialize(const GEdge &ge) { return ge.alive && ge.kind == SPG_EDGE_BINARY && ge.nv == 2 && ge.vtx[0] != ge.vtx[1]; }
+
+void build_spanning_tree(const spg_graph *g, int fixed, SpanningTree &T) {
+    const double PI = 3.14159265358979323846;
+    const int d = g->d, ps = g->ps;
+    const size_t nv = g->vid.size();
+    for (const GEdge &ge : g->edges) if (ge.alive) (enters_initialize(ge) ? T.used : T.ignored)++;
+    T.level.assign(nv, -1);
+    T.tree.assign(nv * ps, 0.0);
+    std::vector<int32_t> parent(nv, -1), pedge(nv, -1), frontier{(int32_t)fixed}, next;
+    T.level[fixed] = 0;
+    memcpy(T.tree.data() + (size_t)fixed * ps, g->host.data() + g->vpose[fixed], (size_t)ps * 8);
+    for (int L = 0; !frontier.empty(); L++) {
+        T.depth = L;
+        next.clear();
+        for (int32_t v : frontier)
+            for (const auto &a : g->vr[v].adj) {
+                const GEdge &ge = g->edges[a.eid];
+                if (!enters_initialize(ge)) continue;
+                const int32_t u = ge.vtx[0] == v ? ge.vtx[1] : ge.vtx[0];
+                if (T.level[u] < 0) { T.level[u] = L + 1; next.push_back(u); parent[u] = v; pedge[u] = a.eid; }
+                else if (T.level[u] == L + 1 &&
+                         (g->vid[v] < g->vid[parent[u]] || (v == parent[u] && a.eid < pedge[u]))) { parent[u] = v; pedge[u] = a.eid; }
+            }
+        // every parent of the level is final: compose
+        for (int32_t u : next) {
+            const GEdge &ge = g->edges[pedge[u]];
+            const double *Z = g->host.data() + ge.off, *Tp = T.tree.data() + (size_t)parent[u] * ps;
+            double *Tc = T.tree.data() + (size_t)u * ps, zi[7];
+            if (ge.vtx[0] == parent[u]) pose_compose(d, Tp, Z, Tc);
+            else { pose_inverse(d, Z, zi); pose_compose(d, Tp, zi, Tc); }
+            if (d == 3) { if (Tc[2] <= -PI) Tc[2] += 2 * PI; }
+            else if (Tc[6] < 0) for (int i = 3; i < 7; i++) Tc[i] = -Tc[i];
+        }
+        frontier.swap(next);
+    }
+}
+
+// mean diagonal of the rotation (rot = true) or translation block of a binary edge's information
+double init_weight(int d, const double *rec, bool rot) {
+    const int ps = pose_stride(d);
+    auto dg = [&](int i) { return rec[ps + i * d - i * (i - 1) / 2]; };
+    if (d == 6) return rot ? (dg(3) + dg(4) + dg(5)) / 3.0 : (dg(0) + dg(1) + dg(2)) / 3.0;
+    return rot ? dg(2) : (dg(0) + dg(1)) / 2.0;
+}
+
+}  // namespace
+
+extern "C" int spg_graph_initialize(spg_graph *g, int method, int32_t fixed_id, spg_init_stats *out) {
+    if (!g || g->active) return SPG_EINVAL;
+    spg_ctx *ctx = g->ctx;
+    if (method != SPG_INIT_SPANNING_TREE && method != SPG_INIT_CHORDAL) return set_err(ctx, SPG_EINVAL, "spg_graph_initialize: unknown method");
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(ctx, SPG_EINVAL, "spg_graph_initialize: the fixed vertex is not in the graph");
+    if (method == SPG_INIT_CHORDAL && !ctx->is_hip) return set_err(ctx, SPG_ESTATE, "spg_graph_initialize: SPG_INIT_CHORDAL needs the HIP backend");
+    canonicalize_edge_order(g);
+    if (int rc = sync_host(g)) return rc;
+    SpanningTree T;
+    build_spanning_tree(g, fixed, T);
+    for (int32_t v : order)
+        if (T.level[v] < 0) {
+            snprintf(ctx->err, sizeof ctx->err, "spg_graph_initialize: vertex %d is not reachable from the fixed vertex %d over binary edges",
+                     (int)g->vid[v], (int)g->vid[fixed]);
+            return SPG_EINVAL;
+        }
+    if (method == SPG_INIT_CHORDAL)
+        for (const GEdge &ge : g->edges) {
+            if (!enters_initialize(ge)) continue;
+            const double kappa = init_weight(g->d, g->host.data() + ge.off, true), tau = init_weight(g->d, g->host.data() + ge.off, false);
+            if (!(std::isfinite(kappa) && std::isfinite(tau) && kappa > 0 && tau > 0)) {
+                snprintf(ctx->err, sizeof ctx->err, "spg_graph_initialize: edge (%d, %d) has a rotation or translation weight that is not finite and positive",
+                         (int)g->vid[ge.vtx[0]], (int)g->vid[ge.vtx[1]]);
+                return SPG_EINVAL;
+            }
+        }
+    spg_init_stats is{};
+    is.method = method; is.n_vertices = (int32_t)order.size(); is.edges_used = T.used; is.edges_ignored = T.ignored; is.tree_depth = T.depth;
+    is.chi2_before = is.chi2_after = std::nan("");
+    if (ctx->is_hip) if (int rc = graph_chi2(g, &is.chi2_before)) return rc;
+    if (order.size() > 1) {
+        // the arena range that holds the free vertices' poses
+        int64_t lo = INT64_MAX, hi = -1;
+        for (int32_t v : order) if (v != fixed) { lo = std::min(lo, g->vpose[v]); hi = std::max(hi, g->vpose[v] + g->ps); }
+        if (method == SPG_INIT_SPANNING_TREE) {
+            if (int rc = ctx->be.synchronize(ctx->be.user)) return rc;
+            for (int32_t v : order) if (v != fixed) memcpy(g->host.data() + g->vpose[v], T.tree.data() + (size_t)v * g->ps, (size_t)g->ps * 8);
+            // one upload of that range as far as the device holds it (the rest follows with the next sync_device)
+            const int64_t top = std::min(hi, g->dev_synced);
+            if (g->dev && top > lo)
+                if (int rc = ctx->be.upload(ctx->be.user, (char *)g->dev + lo * 8, g->host.data() + lo, top - lo)) return rc;
+        } else {
+            DenseStage st;
+            if (int rc = stage_global(g, order, {(int32_t)fixed}, 1, st)) return rc;
+            if (int rc = spg::hip_chordal_init(spg::hip_backend_stream(&ctx->be), st.in, fixed, T.tree.data(), is, ctx->err, sizeof ctx->err)) return rc;
+            std::vector<double> tmp((size_t)(hi - lo));
+            if (int rc = ctx->be.download(ctx->be.user, tmp.data(), (char *)g->dev + lo * 8, hi - lo)) return rc;
+            for (int32_t v : order) if (v != fixed) memcpy(g->host.data() + g->vpose[v], tmp.data() + (g->vpose[v] - lo), (size_t)g->ps * 8);
+        }
+    }
+    if (ctx->is_hip) if (int rc = graph_chi2(g, &is.chi2_after)) return rc;
+    if (out) *out = is;
     return 0;
 }

@@ -132,6 +132,12 @@ int hip_pcg_optimize(void *stream, const DenseGraphIn &in, const bsr::Pattern &P
                      spg_optimize_stats &out, spg_pcg_stats &pcg, char *err, size_t errlen);
 int hip_bsr_bench(void *stream, const DenseGraphIn &in, const bsr::Pattern &P, int reps, double *out, char *err, size_t errlen);
 
+// Chordal initialisation (spg_init.inc): both linear systems of spg_graph_initialize(SPG_INIT_CHORDAL) over one plan of
+// the multifrontal solver with 3 x 3 blocks. in.pos >= 0: the free vertices (ascending = block order), fixed_v: the
+// fixed vertex (index), tree: the spanning-tree poses per vertex index (host, in.nv pose strides) for degenerate
+// vertices. Writes the free vertices' poses into the device arena only when everything succeeded.
+int hip_chordal_init(void *stream, const DenseGraphIn &in, int fixed_v, const double *tree, spg_init_stats &out, char *err, size_t errlen);
+
 // Interior-point NFR (spg_nfr_ip.hip): blankets of the Dense / Subgraph patterns without a closed form, one workgroup
 // each, everything in a per-blanket slice of a global workspace.
 struct IpArgs {

@@ -191,6 +191,16 @@ class GraphWrapperHIP:
         self.last_optimize_stats = st.asdict()
         return self.last_optimize_stats
 
+    def initialize(self, method=abi.INIT_CHORDAL, fixed_id=-1):
+        """spg_graph_initialize: initial estimates from the measurements alone, the step before optimize() for a graph
+        whose stored poses are poor. abi.INIT_CHORDAL: chordal relaxation on the device (rotations, projection, translations;
+        two block-sparse factorisations); abi.INIT_SPANNING_TREE: g2o's computeInitialGuess on the host (any backend).
+        The fixed vertex (fixed_id < 0: the smallest id) keeps its pose. Returns the stats dict."""
+        st = abi.InitStats()
+        check(self.L.spg_graph_initialize(self.h, int(method), int(fixed_id), C.byref(st)), self.ctx.h, "initialize")
+        self.last_init_stats = st.asdict()
+        return self.last_init_stats
+
     def chi2(self, other=None, iterations=50):
         """GraphWrapperG2O::chi2() / chi2(other) (src/graph_wrapper_g2o.cpp:501-529). Without `other`: the
         chi2 of the current estimates. With it: this graph's vertices that also exist in `other` are set

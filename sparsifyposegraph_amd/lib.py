@@ -81,6 +81,7 @@ SYMBOLS = {
     "spg_graph_optimize": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(abi.OptimizeStats)]),
     "spg_graph_optimize_fixed": (C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_int, C.POINTER(abi.OptimizeStats)]),
     "spg_graph_chi2": (C.c_int, [C.c_void_p, _f64p]),
+    "spg_graph_initialize": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(abi.InitStats)]),
     "spg_graph_set_robust_kernel": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
     "spg_graph_get_robust_kernel": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int)]),
     "spg_graph_edge_chi2": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, C.c_int]),
