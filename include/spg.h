@@ -65,10 +65,13 @@ enum {
     SPG_INFO_IP_HESSIAN_NOT_PD = 4, /* interior point: a Newton system was not positive definite and that barrier step was given up
                                     (src/pqn/pqn_optimizer.cpp:48-53 solves with the failed LLT unchecked; the loop over rho,
                                     src/optimizer.cpp:60-75, goes on from the same x either way) */
-    SPG_INFO_GLC_KLD_SKIPPED = 8 /* SPG_FLAG_GLC_KLD was set, but the per-blanket KLD of this GLC blanket is not defined by the
+    SPG_INFO_GLC_KLD_SKIPPED = 8, /* SPG_FLAG_GLC_KLD was set, but the per-blanket KLD of this GLC blanket is not defined by the
                                     gauge route and stays NaN: trace(C^-1) >= 5e4 (the NFR route's guard), the tail cut an
                                     eigenvalue of the target (the edges carry fewer than n - d rows), a root edge was emitted, a
                                     Cholesky factorisation failed, or the blanket took the large-blanket pipeline */
+    SPG_INFO_FD_MAX_CYCLES = 16 /* SPG_FLAG_NFR_FACTOR_DESCENT: the descent of this blanket ended at max_cycles, not at the stop rule
+                                    (always so when spg_ctx_set_factor_descent asked for a fixed number of cycles). Not an error:
+                                    every cycle lowers the KLD, and the edges are those of the last cycle. */
 };
 
 enum {
@@ -91,7 +94,7 @@ enum {
     SPG_FLAG_RESERVED0 = 1, /* bit 0 is reserved (the oracle uses it for a private GLC diagnostic) */
     SPG_FLAG_FORCE_EIG = 2, /* always take the eigen-decomposition route of src/logdet_function.cpp:14-64
                                (default: the equivalent gauge/Cholesky route whenever its guard holds) */
-    SPG_FLAG_GLC_KLD = 4    /* GLC only: also compute the per-blanket KLD of every removal (the reference's GLC provider has no
+    SPG_FLAG_GLC_KLD = 4,   /* GLC only: also compute the per-blanket KLD of every removal (the reference's GLC provider has no
                                LogdetFunction and reports none). With A = sum_e (W_e G_e)^T (W_e G_e) over the emitted edges (G_e =
                                the reparametrisation Jacobian), N^ the orthonormal gauge basis and C = Lambda_t + N^ N^^T:
                                    kld = 1/2 (tr(C^-1 A) - log det(A + N^ N^^T) + log det C - (n - d)),
@@ -100,6 +103,24 @@ enum {
                                like the NFR one. Where it is not defined the blanket reports NaN + SPG_INFO_GLC_KLD_SKIPPED;
                                the large-blanket pipeline (GLC Dense beyond the LDS kernel) never computes it. Backends other
                                than the HIP one may ignore the flag. Clear (default): kld stays NaN for GLC. */
+    SPG_FLAG_NFR_FACTOR_DESCENT = 8,
+                            /* NFR only, and only the blankets whose pattern is uncorrelated with more than k - 1 edges (Subgraph,
+                               Dense): the ones the interior point of src/optimizer.cpp:38-79 takes. Their informations come from
+                               factor descent instead (Vallve, Sola, Andrade-Cetto, RA-L 2018): cyclic block-coordinate descent
+                               on the same convex problem, min KLD(X) over the edge informations. With J~_e = J_e U, S the
+                               spectrum of the target, T_e = J~_e S J~_e^T, M = sum_e J~_e^T X_e J~_e and P = M^-1: start at
+                               X_e = T_e^-1; a cycle visits the edges in pattern order and sets, with A = J~_e P J~_e^T,
+                               Psi = A^-1 - X_e, T_e = L L^T and sym(L^T Psi L) = V diag(psi) V^T,
+                                   X_e <- L^-T V diag(max(1 - psi_i, 1e-9)) V^T L^-1,
+                               the exact minimiser over X_e >= 1e-9 T_e^-1 with the other edges fixed (every information stays
+                               positive definite). M is factorised afresh after every cycle; the run stops after the first cycle
+                               whose KLD decrease is <= rel_tol max(1, |KLD|) or after max_cycles (spg_ctx_set_factor_descent;
+                               SPG_INFO_FD_MAX_CYCLES). The cycle count lands in info >> 8, where the interior point reports its
+                               Newton steps. A T_e that is not positive definite: SPG_ST_CLOSED_FORM_NOT_PD, no edges; an M that
+                               is not: SPG_ST_KLD_NOT_PD and the edges of the last completed cycle. No Newton system, so no limit
+                               on d^2 E: k <= 256 as for the closed forms. Every other blanket (Tree and correlated patterns,
+                               tree-shaped Subgraph blankets, GLC) is bit-identical to an unflagged run. Backends other than the
+                               HIP one may ignore the flag. Clear (default): the interior point. */
     /* bits 8..15: diagnostic pipeline truncation used by tools/phase_bench.py */
 };
 
@@ -428,6 +449,11 @@ int spg_ctx_set_linear_solver(spg_ctx *ctx, int solver);
 /* PCG parameters of the context: stop at ||r|| <= rel_tol ||b|| or after max_iter iterations. <= 0: the defaults,
  * rel_tol = 1e-10 and max_iter = min(n, 20000) (g2o iterates up to n). */
 int spg_ctx_set_pcg(spg_ctx *ctx, double rel_tol, int max_iter);
+/* Factor-descent parameters of the context (SPG_FLAG_NFR_FACTOR_DESCENT): stop after the first cycle whose KLD decrease
+ * is <= rel_tol * max(1, |KLD|), or after max_cycles cycles. A value <= 0 selects the default, rel_tol = 1e-12 and
+ * max_cycles = 2000 — except rel_tol == 0 together with max_cycles > 0, which runs exactly max_cycles cycles.
+ * max_cycles > 32767 (the width of the count in info >> 8) is SPG_EINVAL. Contexts of other backends accept and ignore it. */
+int spg_ctx_set_factor_descent(spg_ctx *ctx, double rel_tol, int max_cycles);
 typedef struct {
     int32_t solves, unconverged;         /* linear systems solved by PCG; those that stopped at max_iter */
     int64_t iterations;                  /* CG iterations over all solves */

@@ -285,6 +285,9 @@ public:
     void setLinearSolver(int solver) { check(spg_ctx_set_linear_solver(_ctx->h, solver), "spg_ctx_set_linear_solver"); }
     // SolverPCG: tolerance on ||r|| / ||b|| and iteration cap of each solve (<= 0: defaults); counters of the last optimize()
     void setPcg(double rel_tol, int max_iter) { check(spg_ctx_set_pcg(_ctx->h, rel_tol, max_iter), "spg_ctx_set_pcg"); }
+    // Stop rule of the factor descent (setFactorDescent; spg_ctx_set_factor_descent in include/spg.h): <= 0 = the defaults,
+    // rel_tol == 0 with max_cycles > 0 = exactly that many cycles
+    void setFactorDescentParams(double rel_tol, int max_cycles) { check(spg_ctx_set_factor_descent(_ctx->h, rel_tol, max_cycles), "spg_ctx_set_factor_descent"); }
     spg_pcg_stats pcgStats() const { spg_pcg_stats st{}; check(spg_ctx_pcg_stats(_ctx->h, &st), "spg_ctx_pcg_stats"); return st; }
     GraphWrapperHIP(const GraphWrapperHIP &) = delete;
     GraphWrapperHIP &operator=(const GraphWrapperHIP &) = delete;
@@ -432,7 +435,7 @@ public:
         so.topology = (int)o.topology;
         so.lin_point = (int)o.linPoint;
         so.include_intra_clique = o.includeIntraClique ? 1 : 0;
-        so.flags = (_glc && _glc_kld) ? SPG_FLAG_GLC_KLD : 0;
+        so.flags = ((_glc && _glc_kld) ? SPG_FLAG_GLC_KLD : 0) | ((!_glc && _factor_descent) ? SPG_FLAG_NFR_FACTOR_DESCENT : 0);
         so.chord_ratio = o.chordRatio;
         std::vector<int32_t> w(which.begin(), which.end());
         drop_views();
@@ -617,6 +620,10 @@ public:
     // provider has no LogdetFunction. No effect on an NFR graph. Not a member of the reference's SparsityOptions.
     void setGlcBlanketKld(bool on) { _glc_kld = on; }
     bool glcBlanketKld() const { return _glc_kld; }
+    // NFR blankets whose pattern has no closed form (Subgraph / Dense with more than k - 1 edges) by factor descent instead
+    // of the interior point (SPG_FLAG_NFR_FACTOR_DESCENT, include/spg.h): off by default; no effect on a GLC graph
+    void setFactorDescent(bool on) { _factor_descent = on; }
+    bool factorDescent() const { return _factor_descent; }
     const spg_marg_stats &lastStats() const { return _stats; }
     spg_graph *handle() { return _g; }
     spg_ctx *context() { return _ctx->h; }
@@ -688,6 +695,7 @@ private:
     spg_graph *_g = nullptr;
     bool _glc;
     bool _glc_kld = false;
+    bool _factor_descent = false;
     spg_marg_stats _stats{};
     spg_optimize_stats _last_opt{};
     mutable std::vector<Vertex *> _vviews;     // id-sorted

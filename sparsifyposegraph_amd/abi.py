@@ -17,8 +17,10 @@ ST_OK, ST_HMM_NOT_PD, ST_EIG_FAIL, ST_NONFINITE, ST_TIKHONOV_NOT_PD, ST_CLOSED_F
     ST_KLD_NOT_PD, ST_NEEDS_INTERIOR_POINT, ST_MARGINAL_NOT_PD, ST_EMPTY_BLANKET, ST_UNSUPPORTED, \
     ST_NEEDS_LOCAL_OPTIMIZATION = range(12)
 INFO_RANK_DEFICIENT, INFO_GLC_ROOT_EDGE, INFO_IP_HESSIAN_NOT_PD, INFO_GLC_KLD_SKIPPED = 1, 2, 4, 8
+INFO_FD_MAX_CYCLES = 16
 FLAG_FORCE_EIG = 2
 FLAG_GLC_KLD = 4
+FLAG_NFR_FACTOR_DESCENT = 8
 EINVAL, ENODEV, ENOMEM, ECAPACITY, EHIP, EIO, ESTATE, EBLANKET, ENOTPD = -1, -2, -3, -4, -5, -6, -7, -8, -9
 OUT_HDR = 6
 
@@ -34,10 +36,13 @@ class Options(C.Structure):
 
 
 def make_options(pose_dim, algorithm=ALG_NFR, topology=TOPO_TREE, lin_point=LIN_GLOBAL, flags=0,
-                 chord_ratio=1.0, include_intra_clique=1, glc_kld=False):
-    """glc_kld: SPG_FLAG_GLC_KLD — per-blanket KLD of GLC removals (kld is NaN for GLC without it)."""
+                 chord_ratio=1.0, include_intra_clique=1, glc_kld=False, factor_descent=False):
+    """glc_kld: SPG_FLAG_GLC_KLD — per-blanket KLD of GLC removals (kld is NaN for GLC without it).
+    factor_descent: SPG_FLAG_NFR_FACTOR_DESCENT — NFR blankets without a closed form by factor descent, not the interior point."""
     if glc_kld:
         flags |= FLAG_GLC_KLD
+    if factor_descent:
+        flags |= FLAG_NFR_FACTOR_DESCENT
     return Options(pose_dim, algorithm, topology, lin_point, include_intra_clique, flags, chord_ratio)
 
 

@@ -87,6 +87,8 @@ struct HipBackend {
     double prof_worker_ms = 0, prof_worker_bytes = 0;
     long long prof_worker_runs = 0, prof_worker_blankets = 0;
     int lds_limit = 160 * 1024;
+    double fd_rel_tol = kFdRelTol;                    // spg_ctx_set_factor_descent, resolved (0: exactly fd_max_cycles cycles)
+    int fd_max_cycles = kFdMaxCycles;
     bool large_bar = false;       // the host can store straight into device memory (hipDeviceAttributeIsLargeBar)
     std::atomic<int> n_launches{0};
     // environment switches, read once
@@ -485,6 +487,7 @@ int HipBackend::launch_generic(Slot &S, const spg_round_desc *rd, void *arena, c
     ia.list = list;
     ia.ws = (double *)S.ipws.p; ia.ws_stride = P.ip_stride; ia.mail = ka.mail; ia.mail_base = rd->mail_base;
     ia.topology = o.topology; ia.lin_point = o.lin_point; ia.tag = rd->tag; ia.chord_ratio = o.chord_ratio;
+    ia.factor_descent = (o.flags & SPG_FLAG_NFR_FACTOR_DESCENT) ? 1 : 0; ia.fd_rel_tol = fd_rel_tol; ia.fd_max_cycles = fd_max_cycles;
     if (o.lin_point != SPG_LIN_GLOBAL) if (int rc = local_prepass(S, rd, arena, ia)) return rc;
     if (int rc = hip_nfr_ip_launch((void *)S.stream, o.pose_dim, ia, (int)P.ip_list.size(), P.ip_closed, P.ip_hot)) { snprintf(err, sizeof err, "launch of the interior-point kernel failed"); return rc; }
     // (this kernel comes AFTER the event a bin launch left in wait_ev: waiting for the slot must mean the whole stream.
@@ -718,6 +721,11 @@ void hip_backend_profile_read_big(spg_backend *b, double *ms, double *flops, lon
     HipBackend *hb = (HipBackend *)b->user;
     if (!hb) return;
     *ms = hb->prof_big_ms; *flops = hb->prof_big_flops; *count = hb->prof_big_count; *nmax = hb->prof_big_nmax;
+}
+void hip_backend_set_factor_descent(spg_backend *b, double rel_tol, int max_cycles) {
+    if (!b->user) return;
+    HipBackend *hb = (HipBackend *)b->user;
+    hb->fd_rel_tol = rel_tol; hb->fd_max_cycles = max_cycles;
 }
 int hip_backend_end_of_call(spg_backend *b) {
     HipBackend *hb = (HipBackend *)b->user;

@@ -110,6 +110,14 @@ extern "C" int spg_ctx_set_pcg(spg_ctx *c, double rel_tol, int max_iter) {
     c->pcg_max_iter = max_iter > 0 ? max_iter : 0;
     return 0;
 }
+extern "C" int spg_ctx_set_factor_descent(spg_ctx *c, double rel_tol, int max_cycles) {
+    if (!c || std::isnan(rel_tol) || max_cycles > 32767) return SPG_EINVAL;
+    // rel_tol == 0 with a cycle count: exactly that many cycles; otherwise a value <= 0 selects the default
+    const int cycles = max_cycles > 0 ? max_cycles : spg::kFdMaxCycles;
+    const double tol = rel_tol > 0 ? rel_tol : (rel_tol == 0 && max_cycles > 0) ? 0.0 : spg::kFdRelTol;
+    if (c->is_hip) spg::hip_backend_set_factor_descent(&c->be, tol, cycles);    // (other backends ignore the flag)
+    return 0;
+}
 extern "C" int spg_ctx_pcg_stats(spg_ctx *c, spg_pcg_stats *out) {
     if (!c || !out) return SPG_EINVAL;
     *out = c->pcg_stats;

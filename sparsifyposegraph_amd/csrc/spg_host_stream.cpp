@@ -776,7 +776,7 @@ int stream_marginalize(spg_graph *g, bool *started) {
     const bool emulate = !g->ctx->is_hip && !sim;
     if (env_off || g->stream_disabled) return 1;
     if (emulate && g->stream_emulation < 0) return 1;
-    if (g->nranks != 1 || o.algorithm != SPG_ALG_NFR || o.topology != SPG_TOPO_TREE || o.lin_point != SPG_LIN_GLOBAL || o.flags != 0) return 1;
+    if (g->nranks != 1 || o.algorithm != SPG_ALG_NFR || o.topology != SPG_TOPO_TREE || o.lin_point != SPG_LIN_GLOBAL || (o.flags & ~SPG_FLAG_NFR_FACTOR_DESCENT) != 0) return 1;
     const int32_t P = (int32_t)g->pending.size();
     if (P < (emulate ? 1 : 64)) return 1;   // a handful of removals (online decimation): one plain launch is cheaper than starting the worker
     Streamer S(g, emulate);

@@ -17,6 +17,7 @@ void hip_backend_profile(spg_backend *b, int enable);
 void hip_backend_profile_read(spg_backend *b, double *ms, double *bytes, long long *launches, long long *blankets);
 void hip_backend_profile_read_worker(spg_backend *b, double *ms, double *bytes, long long *runs, long long *blankets);
 void hip_backend_profile_read_big(spg_backend *b, double *ms, double *flops, long long *count, int *nmax);
+void hip_backend_set_factor_descent(spg_backend *b, double rel_tol, int max_cycles);   // as spg_ctx_set_factor_descent resolved them
 int hip_backend_end_of_call(spg_backend *b);   // the persistent worker retires (end of a marginalisation)
 
 // ---- queue of the persistent worker kernel (blanket_worker, spg_kernels.hip): fine-grained device memory the host
@@ -156,11 +157,18 @@ struct IpArgs {
     int eig_jacobi;           // diagnostic (SPG_EIG_JACOBI=1): Jacobi sweeps for the spectrum of large targets too
     int ip_untiled;           // diagnostic (SPG_IP_UNTILED=1): the column-at-a-time LDS factorisation instead of the register-tiled one
     double chord_ratio;
+    // SPG_FLAG_NFR_FACTOR_DESCENT (spg_nfr_fd.inc): the blankets without a closed form by factor descent instead of the interior
+    // point; stop at a KLD decrease <= fd_rel_tol max(1, |KLD|) (0: never, exactly fd_max_cycles cycles) or after fd_max_cycles
+    int factor_descent, fd_max_cycles;
+    double fd_rel_tol;
 };
+constexpr double kFdRelTol = 1e-12;  // defaults of spg_ctx_set_factor_descent
+constexpr int kFdMaxCycles = 2000;
 constexpr int kIpMaxVars = 8400;     // Newton systems of the interior point: d^2 E up to this (k = 22 SE3 / 43 SE2 poses under Dense: what
                                      // parking.g2o's largest blanket asks for); one workgroup factorises them: minutes per blanket at the top
 int nfr_ip_pattern_size(int topology, double chord_ratio, int k);   // new edges of a blanket with k kept vertices (-1: correlated patterns)
 int64_t nfr_ip_workspace(int D, int k, int m, int E, int closed, int64_t *hot);  // doubles of workspace one such blanket needs (*hot: its LDS-eligible part)
+int64_t nfr_fd_workspace(int D, int k, int m, int E, int64_t *hot);   // ... of a blanket without a closed form under SPG_FLAG_NFR_FACTOR_DESCENT
 int hip_nfr_ip_launch(void *stream, int D, IpArgs a, int count, int n_closed, int64_t hot_max);   // n_closed of the blankets have a closed-form pattern
 
 // RCCL binding (spg_rccl.cpp): librccl.so.1 is bound with dlopen when the first multi-rank context is created

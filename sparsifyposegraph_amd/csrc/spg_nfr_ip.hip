@@ -56,13 +56,15 @@ struct IpLayout {   // offsets (doubles) of one blanket's buffers: a cold part i
     int64_t total;
 };
 
-__host__ __device__ inline IpLayout ip_layout(int D, int k, int m, int E, bool closed) {
+// fd (factor descent, spg_nfr_fd.inc): no Hessian and no Newton vectors — P = M^-1 lives in Mi; the X_e, their copy of the last
+// completed cycle, L_e and L_e^-1 in the x / xn / g / gn blocks, blockdiag(X) J U in dv, J~_e P and K J~_e P (2 d x r) in P
+__host__ __device__ inline IpLayout ip_layout(int D, int k, int m, int E, bool closed, bool fd = false) {
     IpLayout L;
     L.n = D * k; L.nm = D * m; L.N = L.n + L.nm; L.r = L.n - D; L.E = E; L.q = D * E; L.nx = D * D * E;
     int64_t o = 0;
     auto take = [&](int64_t len) { int64_t at = o; o += (len + 7) & ~(int64_t)7; return at; };
     const int64_t n = L.n, N = L.N, r = L.r > 0 ? L.r : 1, q = L.q, nx = L.nx, P2 = (int64_t)k * (k - 1) / 2;
-    L.H = take(N * N); L.Lam = take(n * n); L.A1 = take(n * n); L.V = take(n * n); L.Hx = take(closed ? 8 : (nx + 8) * (nx + 8) + 64 * (nx + 8));   // rows of nx + 8 doubles, nx + 8 of them: whole 8 x 8 tiles everywhere (no Newton iterations when the pattern has a closed form)
+    L.H = take(N * N); L.Lam = take(n * n); L.A1 = take(n * n); L.V = take(n * n); L.Hx = take((closed || fd) ? 8 : (nx + 8) * (nx + 8) + 64 * (nx + 8));   // rows of nx + 8 doubles, nx + 8 of them: whole 8 x 8 tiles everywhere (no Newton iterations when the pattern has a closed form)
     L.pose = take(12 * (int64_t)(k + m)); L.w = take(4 * P2 + 8);
     L.Sc = take(3 * N * N + 5 * n * n);            // correlated input edges (J, W J), closed form of correlated new edges (J_e, G, C, W, X)
     L.zbuf = take(7 * (int64_t)(E + 1)); L.grp = take(2 * (int64_t)k + 8); L.otab = take(8 * (int64_t)k + 8);
@@ -72,8 +74,8 @@ __host__ __device__ inline IpLayout ip_layout(int D, int k, int m, int E, bool c
     o = 0;
     L.S = take(n); L.U = take(n * r); L.J = take(2 * (int64_t)D * D * E); L.JU = take(q * r); L.Ai = take(n * n); L.T1 = take(n * r);
     L.M = take(r * r); L.Mc = take(r * r); L.Mi = take(r * r); L.Li = take(r * r); L.Y = take(n * n);
-    L.P = take(q * q); L.T2 = take(q * r);
-    L.x = take(nx); L.xn = take(nx); L.g = take(nx); L.gn = take(nx); L.dv = take(nx); L.Xi = take(nx);
+    L.P = take(fd ? 2 * (int64_t)D * r : q * q); L.T2 = take(fd ? 8 : q * r);
+    L.x = take(nx); L.xn = take(nx); L.g = take(nx); L.gn = take(nx); L.dv = take(fd ? q * r : nx); L.Xi = take(fd ? 8 : nx);
     L.hot_total = o;
     L.total = L.cold_total + L.hot_total;
     return L;
@@ -418,8 +420,11 @@ __device__ void chol_lower_panel(const Team<NT_> T, double *A, int n, int ld, do
 // Each leaves the other's blankets alone, and the compiler drops the other's code: with both in one kernel the register
 // allocation of the interior point's two-tiles-per-thread factorisation degraded by half (sphere.g2o under Subgraph:
 // 3.3 -> 4.4 s) once the cluster routines had grown.
-template <int D, bool CLOSED>
+// FD (with !CLOSED only): the interior point's blankets by factor descent (SPG_FLAG_NFR_FACTOR_DESCENT) — a third
+// instantiation for the same reason, so that the unflagged kernels are the code they were.
+template <int D, bool CLOSED, bool FD = false>
 __global__ __launch_bounds__(NT) void nfr_ip_kernel(spg::IpArgs a) {
+    static_assert(!(CLOSED && FD), "factor descent replaces the interior point only");
     constexpr int DD = D * D, PS = (D == 6) ? 7 : 3, PSZ = (D == 6) ? 12 : 3, REC = PS + D * (D + 1) / 2;
     extern __shared__ double lds_pool[];
     __shared__ double red[NT];
@@ -438,7 +443,7 @@ __global__ __launch_bounds__(NT) void nfr_ip_kernel(spg::IpArgs a) {
     // pattern, and the uncorrelated ones that are trees (they come here when the blanket holds correlated input edges)
     if ((cliquey || E <= k - 1) != CLOSED) return;        // the other instantiation's blanket
     constexpr bool closed = CLOSED;
-    const IpLayout L = ip_layout(D, k, m, E > 0 ? E : 1, closed);
+    const IpLayout L = ip_layout(D, k, m, E > 0 ? E : 1, closed, FD);
     const int n = L.n, nm = L.nm, N = L.N, r = L.r, q = L.q, nx = L.nx;
     double *ws = a.ws + (int64_t)blockIdx.x * a.ws_stride;
     // hot buffers in LDS when this blanket's fit into what the launch reserved (latency per dependent phase ~0.1 us
@@ -459,6 +464,7 @@ __global__ __launch_bounds__(NT) void nfr_ip_kernel(spg::IpArgs a) {
     const long long packed_pad = (packed_len + 1) & ~1LL;
     double *hot = hx_lds ? ((packed_pad + L.hot_total <= (int64_t)a.lds_doubles) ? lds_pool + packed_pad : ws + L.cold_total)
                          : ((kPanelDoubles + L.hot_total <= (int64_t)a.lds_doubles) ? lds_pool + kPanelDoubles : ws + L.cold_total);
+    if constexpr (FD) hot = (L.hot_total <= (int64_t)a.lds_doubles) ? lds_pool : ws + L.cold_total;     // no Hessian, no panel: the whole dynamic LDS
     double *arena = a.arena;
     double *orec = a.mail ? (a.mail + (bd.out_off - a.mail_base)) : (arena + bd.out_off);
     if (tid == 0) flag_s = 0;
@@ -1419,6 +1425,9 @@ __global__ __launch_bounds__(NT) void nfr_ip_kernel(spg::IpArgs a) {
         JU[it] = s;
     }
     __syncthreads();
+    if constexpr (FD) {
+#include "spg_nfr_fd.inc"
+    }
 
     // ---- the function: value(xv) leaves chol(M) in Mc; gradient(xv, gv) leaves M^-1 in Mi and the X_e^-1 in Xi
     double *P = hot + L.P, *T2 = hot + L.T2, *Hx = ws + L.Hx, *Xi = hot + L.Xi;
@@ -2270,6 +2279,12 @@ int64_t nfr_ip_workspace(int D, int k, int m, int E, int closed, int64_t *hot) {
     return L.total;
 }
 
+int64_t nfr_fd_workspace(int D, int k, int m, int E, int64_t *hot) {
+    const IpLayout L = ip_layout(D, k, m, E > 0 ? E : 1, false, true);
+    if (hot) *hot = L.hot_total;
+    return L.total;
+}
+
 int hip_nfr_ip_launch(void *stream, int D, IpArgs a, int count, int n_closed, int64_t hot_max) {
     if (count <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -2288,14 +2303,15 @@ int hip_nfr_ip_launch(void *stream, int D, IpArgs a, int count, int n_closed, in
     // other's blankets: the workspace slices stay indexed by the position in the list)
     for (int closed = 0; closed < 2; closed++) {
         if ((closed ? n_closed : count - n_closed) <= 0) continue;
-        const void *fn = D == 6 ? (closed ? reinterpret_cast<const void *>(nfr_ip_kernel<6, true>) : reinterpret_cast<const void *>(nfr_ip_kernel<6, false>))
-                                : (closed ? reinterpret_cast<const void *>(nfr_ip_kernel<3, true>) : reinterpret_cast<const void *>(nfr_ip_kernel<3, false>));
+        const bool fd = !closed && a.factor_descent;     // the blankets without a closed form by factor descent (spg_nfr_fd.inc)
+        const void *fn = D == 6 ? (closed ? reinterpret_cast<const void *>(nfr_ip_kernel<6, true>) : fd ? reinterpret_cast<const void *>(nfr_ip_kernel<6, false, true>) : reinterpret_cast<const void *>(nfr_ip_kernel<6, false>))
+                                : (closed ? reinterpret_cast<const void *>(nfr_ip_kernel<3, true>) : fd ? reinterpret_cast<const void *>(nfr_ip_kernel<3, false, true>) : reinterpret_cast<const void *>(nfr_ip_kernel<3, false>));
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
             return SPG_EHIP;
         }
-        if (D == 6) { if (closed) hipLaunchKernelGGL((nfr_ip_kernel<6, true>), dim3(count), dim3(NT), lds, s, a); else hipLaunchKernelGGL((nfr_ip_kernel<6, false>), dim3(count), dim3(NT), lds, s, a); }
-        else { if (closed) hipLaunchKernelGGL((nfr_ip_kernel<3, true>), dim3(count), dim3(NT), lds, s, a); else hipLaunchKernelGGL((nfr_ip_kernel<3, false>), dim3(count), dim3(NT), lds, s, a); }
+        if (D == 6) { if (closed) hipLaunchKernelGGL((nfr_ip_kernel<6, true>), dim3(count), dim3(NT), lds, s, a); else if (fd) hipLaunchKernelGGL((nfr_ip_kernel<6, false, true>), dim3(count), dim3(NT), lds, s, a); else hipLaunchKernelGGL((nfr_ip_kernel<6, false>), dim3(count), dim3(NT), lds, s, a); }
+        else { if (closed) hipLaunchKernelGGL((nfr_ip_kernel<3, true>), dim3(count), dim3(NT), lds, s, a); else if (fd) hipLaunchKernelGGL((nfr_ip_kernel<3, false, true>), dim3(count), dim3(NT), lds, s, a); else hipLaunchKernelGGL((nfr_ip_kernel<3, false>), dim3(count), dim3(NT), lds, s, a); }
         if (hipGetLastError() != hipSuccess) return SPG_EHIP;
     }
     return 0;

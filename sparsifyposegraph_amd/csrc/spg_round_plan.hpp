@@ -75,7 +75,7 @@ inline void plan_worker(const spg_round_desc *rd, const PlanConfig &cfg, const W
     // (not for the first two batches after a synchronisation: a call that removes a handful of vertices, e.g. online
     //  decimation, is cheaper as a plain launch than as worker start + stop)
     bool to_worker = cfg.worker_enabled && cfg.large_bar && rd->mail_len > 0 && o.algorithm == SPG_ALG_NFR && o.topology == SPG_TOPO_TREE &&
-                     o.lin_point == SPG_LIN_GLOBAL && o.flags == 0 && rd->count <= 512 && !cfg.force_one_wave &&
+                     o.lin_point == SPG_LIN_GLOBAL && (o.flags & ~SPG_FLAG_NFR_FACTOR_DESCENT) == 0 && rd->count <= 512 && !cfg.force_one_wave &&
                      ws.cooldown == 0 && (ws.batches_in_call > 2 || ws.running);
     P.cooldown = ws.cooldown > 0 ? ws.cooldown - 1 : 0;
     if (to_worker) {
@@ -140,6 +140,9 @@ inline int plan_generic(const spg_round_desc *rd, const PlanConfig &cfg, RoundPl
     const int D = o.pose_dim;
     if (o.algorithm != SPG_ALG_NFR) return 0;
     const bool cliquey = o.topology == SPG_TOPO_CLIQUEY_SUBGRAPH || o.topology == SPG_TOPO_CLIQUEY_DENSE;
+    // SPG_FLAG_NFR_FACTOR_DESCENT: the blankets of the interior point go through factor descent (spg_nfr_fd.inc) — no Newton
+    // system, so no kIpMaxVars, and a workspace without the (d^2 E)^2 Hessian
+    const bool fd = (o.flags & SPG_FLAG_NFR_FACTOR_DESCENT) != 0;
     int rc = 0;
     for (int i = 0; i < kPlanBins && !rc; i++) {
         filter_bin(rd, P.bins[i], [&](int32_t b) {
@@ -162,7 +165,7 @@ inline int plan_generic(const spg_round_desc *rd, const PlanConfig &cfg, RoundPl
             const bool masks = o.topology == SPG_TOPO_CLIQUEY_SUBGRAPH && msub < k * (k - 1) / 2;   // fillCliques on 64-bit vertex masks
             // (interior point: Newton systems up to 2 048 variables in LDS-resident forms, up to kIpMaxVars through the
             //  blocked factorisation — one workgroup, 0.1 s per Newton step at 2 400 variables, 1 s at 4 900, 5 s at 8 300)
-            if ((ip && (int64_t)D * D * E > kIpMaxVars) || (masks && k > 64) || k > 256) {
+            if ((ip && !fd && (int64_t)D * D * E > kIpMaxVars) || (masks && k > 64) || k > 256) {
                 snprintf(err, errlen, "interior-point / correlated NFR: a blanket with k=%d kept vertices and %d new measurements is beyond the generic kernel (Newton systems up to %d variables; k <= 64 for CliqueySubgraph, 256 otherwise)", k, E, kIpMaxVars);
                 rc = SPG_ECAPACITY;
                 return true;
@@ -170,7 +173,7 @@ inline int plan_generic(const spg_round_desc *rd, const PlanConfig &cfg, RoundPl
             P.ip_list.push_back(b);
             if (!ip) P.ip_closed++;        // (closed form: every correlated pattern, trees with correlated input edges)
             int64_t hot = 0;
-            P.ip_stride = std::max(P.ip_stride, nfr_ip_workspace(D, k, m, E, ip ? 0 : 1, &hot));
+            P.ip_stride = std::max(P.ip_stride, (ip && fd) ? nfr_fd_workspace(D, k, m, E, &hot) : nfr_ip_workspace(D, k, m, E, ip ? 0 : 1, &hot));
             P.ip_hot = std::max(P.ip_hot, hot);
             return false;
         });

@@ -81,6 +81,7 @@ class GraphWrapperHIP:
         self.d = self.L.spg_graph_pose_dim(self.h)
         self.last_stats = None
         self.glcBlanketKld = False   # setGlcBlanketKld
+        self.factorDescent = False   # setFactorDescent
         self.ctx._track(self)
 
     # ---- construction -------------------------------------------------------------------
@@ -141,8 +142,16 @@ class GraphWrapperHIP:
         useGLC graph: an abi.Options argument carries its own flags (abi.make_options(..., glc_kld=True))."""
         self.glcBlanketKld = bool(on)
 
+    def setFactorDescent(self, on=True):
+        """NFR blankets whose pattern has no closed form (Subgraph / Dense with more than k - 1 edges) by factor descent
+        instead of the interior point (SPG_FLAG_NFR_FACTOR_DESCENT, include/spg.h; Context.set_factor_descent for the stop
+        rule) in the marginalisations that follow; off by default. Only applies to SparsityOptions arguments of an NFR
+        graph: an abi.Options argument carries its own flags (abi.make_options(..., factor_descent=True))."""
+        self.factorDescent = bool(on)
+
     def _flags(self, flags):
-        return flags | (abi.FLAG_GLC_KLD if (self.useGLC and self.glcBlanketKld) else 0)
+        return flags | (abi.FLAG_GLC_KLD if (self.useGLC and self.glcBlanketKld) else 0) \
+                     | (abi.FLAG_NFR_FACTOR_DESCENT if (not self.useGLC and self.factorDescent) else 0)
 
     def marginalizeNoOptimize(self, which, options, flags=0):
         """src/graph_wrapper_g2o.cpp:398-453"""

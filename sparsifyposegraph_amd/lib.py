@@ -75,6 +75,7 @@ SYMBOLS = {
     "spg_graph_joint_marginal_covariance": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
+    "spg_ctx_set_factor_descent": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "spg_ctx_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(abi.PcgStats)]),
     "spg_sparse_plan": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.POINTER(abi.SparsePlanInfo),
                                   _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int64]),
@@ -205,6 +206,12 @@ class Context:
         """spg_ctx_set_pcg: stop PCG at ||r|| <= rel_tol ||b|| or after max_iter iterations; <= 0: the defaults
         (1e-10, min(n, 20000))."""
         check(self.L.spg_ctx_set_pcg(self.h, float(rel_tol), int(max_iter)), self.h, "spg_ctx_set_pcg")
+
+    def set_factor_descent(self, rel_tol=0.0, max_cycles=0):
+        """spg_ctx_set_factor_descent (abi.FLAG_NFR_FACTOR_DESCENT): stop after the first cycle whose KLD decrease is
+        <= rel_tol max(1, |KLD|) or after max_cycles; <= 0: the defaults (1e-12, 2000); rel_tol == 0 with
+        max_cycles > 0: exactly that many cycles."""
+        check(self.L.spg_ctx_set_factor_descent(self.h, float(rel_tol), int(max_cycles)), self.h, "spg_ctx_set_factor_descent")
 
     def pcg_stats(self):
         """spg_ctx_pcg_stats: PCG counters of the context's last optimize call (all zero if it did not run PCG)."""
