@@ -429,6 +429,35 @@ int64_t spg_graph_pair_covariances(spg_graph *g, int32_t fixed_id, const int32_t
 int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fixed_id, const int32_t *ids, int n, double *out, int64_t cap,
                                             spg_cov_solve_stats *stats);
 
+/* ---- relative-pose covariances and loop-closure candidate scores --------------------------------------
+ * How uncertain the graph is about b as seen from a. For a hypothetical binary edge a -> b with measurement z and
+ * information Omega: e = its error at the stored estimates (toVectorMQT(Z^-1 Xa^-1 Xb) for SE3), J = [Ja Jb] its D x 2D
+ * Jacobian at z with respect to the vertex updates spg_graph_information uses, Sigma_ab the 2D x 2D block of
+ * spg_graph_pair_covariances, P = J Sigma_ab J^T the covariance of that error in the coordinates of Omega. With
+ * Omega = L L^T and M = I + L^T P L (eigenvalues >= 1; Omega^-1 is never formed):
+ *   chi2 = e^T Omega e
+ *   d2   = (L^T e)^T M^-1 (L^T e) = e^T (P + Omega^-1)^-1 e   innovation Mahalanobis distance, chi^2 with D degrees of
+ *                                                             freedom for an inlier
+ *   gain = 1/2 ln det M = 1/2 (ln det H' - ln det H)          nats; H' = the information after adding the edge at the
+ *                                                             same estimates
+ * The relative covariance of (a, b) is P at z = the current relative pose (e = 0); P^-1 is then the information of the
+ * marginal relative-pose factor between a and b, with z a record spg_graph_add_edge accepts. The pair blocks stay on the
+ * device: only D^2 doubles per pair, or the scores, come back. a or b may be the fixed vertex; a pair may be listed many
+ * times (several hypotheses) and costs one cross block. The graph's robust kernel is ignored and the graph is not
+ * modified. Conventions and error codes of spg_graph_pair_covariances; an unknown id, a == b, a non-finite measurement
+ * and an active stepwise marginalisation are SPG_EINVAL (the text names the pair) before the backend is touched. */
+enum { SPG_CAND_SCORED = 0, SPG_CAND_INFO_NOT_PD = 1 };
+/* n pairs of distinct live vertices. rel: n x (3|7), the current relative pose in the measurement layout of spg_graph_add_edge
+ * (may be NULL). cov: n x D x D, row-major, exactly symmetric. Returns n D^2; writes only when cov && cap >= that. */
+int64_t spg_graph_relative_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *rel, double *cov,
+                                       int64_t cap, spg_cov_solve_stats *stats);
+/* n candidate binary edges. ij: n x 2. records: n x (meas + info upper triangle), the layout of spg_graph_add_edges.
+ * d2, gain, chi2: n each, each may be NULL. status: n, may be NULL. 0 = scored. SPG_CAND_INFO_NOT_PD = 1: Omega not positive definite
+ * or not finite; that candidate's three values are NaN and the call still succeeds. Returns n; writes when cap >= n.
+ * The graph is not modified. */
+int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n,
+                               double *d2, double *gain, double *chi2, int32_t *status, int cap, spg_cov_solve_stats *stats);
+
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the
  * smallest id), g2o's Levenberg-Marquardt for up to `iterations` iterations (the reference uses 50),

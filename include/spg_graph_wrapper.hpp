@@ -512,6 +512,56 @@ public:
               "jointMarginalCovariance");
         return split_blocks(buf, 1, (int)w.size() * d)[0];
     }
+    // the relative pose Xa^-1 Xb of each pair of distinct vertices (the numbers of IsometryXd::vector(), exactly as the
+    // device wrote them) and its D x D covariance P = J Sigma_ab J^T (include/spg.h: spg_graph_relative_covariances);
+    // addEdge(a, b, IsometryXd(first), inverse of second) is the marginal relative-pose factor of the pair
+    std::vector<std::pair<VectorXd, MatrixXd>> relativeCovariances(const std::vector<std::pair<int, int>> &pairs, int fixed_id = -1,
+                                                                     spg_cov_solve_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g), ps = d == 3 ? 3 : 7;
+        std::vector<int32_t> p;
+        for (auto &q : pairs) { p.push_back(q.first); p.push_back(q.second); }
+        int64_t need = spg_graph_relative_covariances(_g, fixed_id, p.data(), (int)pairs.size(), nullptr, nullptr, 0, nullptr);
+        check((int)std::min<int64_t>(need, 0), "relativeCovariances");
+        std::vector<double> rel(std::max<size_t>(pairs.size(), 1) * ps), buf((size_t)std::max<int64_t>(need, 1));
+        check((int)std::min<int64_t>(spg_graph_relative_covariances(_g, fixed_id, p.data(), (int)pairs.size(), rel.data(), buf.data(), need, stats), 0),
+              "relativeCovariances");
+        std::vector<MatrixXd> P = split_blocks(buf, (int64_t)pairs.size(), d);
+        std::vector<std::pair<VectorXd, MatrixXd>> out;
+        for (size_t i = 0; i < pairs.size(); i++) out.emplace_back(VectorXd(rel.begin() + i * ps, rel.begin() + (i + 1) * ps), P[i]);
+        return out;
+    }
+    // A hypothetical binary edge and what the graph says about it (include/spg.h: spg_graph_score_candidates)
+    struct Candidate {
+        int from, to;
+        VectorXd measurement;     // SE2 (x y theta), SE3 (t, unit quaternion): IsometryXd::vector(), taken as given
+        MatrixXd information;     // d x d
+    };
+    struct CandidateScore {
+        double d2;      // innovation Mahalanobis distance e^T (P + Omega^-1)^-1 e: chi^2 with d degrees of freedom for an inlier
+        double gain;    // information gain 1/2 ln det(I + Omega P), nats
+        double chi2;    // e^T Omega e
+        int status;     // SPG_CAND_SCORED, or SPG_CAND_INFO_NOT_PD (the three values are NaN)
+    };
+    std::vector<CandidateScore> scoreCandidates(const std::vector<Candidate> &cands, int fixed_id = -1, spg_cov_solve_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g), n = (int)cands.size();
+        std::vector<int32_t> ij;
+        std::vector<double> rec;
+        for (const Candidate &c : cands) {
+            if (c.information.rows() != d || c.information.cols() != d) throw std::runtime_error("scoreCandidates: information must be d x d");
+            const VectorXd &z = c.measurement;
+            if ((int)z.size() != (d == 3 ? 3 : 7)) throw std::runtime_error("scoreCandidates: the measurement does not match the graph's pose dimension");
+            ij.push_back(c.from); ij.push_back(c.to);
+            rec.insert(rec.end(), z.begin(), z.end());
+            for (int i = 0; i < d; i++) for (int j = i; j < d; j++) rec.push_back(c.information(i, j));
+        }
+        std::vector<double> d2((size_t)std::max(n, 1)), gain(d2.size()), chi2(d2.size());
+        std::vector<int32_t> status(d2.size());
+        check(std::min(spg_graph_score_candidates(_g, fixed_id, ij.data(), rec.data(), n, d2.data(), gain.data(), chi2.data(), status.data(), n, stats), 0),
+              "scoreCandidates");
+        std::vector<CandidateScore> out;
+        for (int i = 0; i < n; i++) out.push_back({d2[i], gain[i], chi2[i], (int)status[i]});
+        return out;
+    }
     // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
     // its marginal here, every vertex of `other` but the fixed one; ids ascending
     std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {

@@ -102,6 +102,10 @@ class CovSolveStats(C.Structure):
         return d
 
 
+# SPG_CAND_* (include/spg.h): status of a candidate of spg_graph_score_candidates
+CAND_SCORED, CAND_INFO_NOT_PD = 0, 1
+
+
 class OptimizeStats(C.Structure):
     """spg_optimize_stats (include/spg.h)"""
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),

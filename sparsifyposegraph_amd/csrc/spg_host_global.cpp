@@ -459,6 +459,72 @@ extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fix
     return cov_solve(g, fixed, order, va, vb, dst, (int32_t)W, need, out, stats, "spg_graph_joint_marginal_covariance");
 }
 
+// ================================================================================= relative covariances, candidate scores
+namespace {
+// What spg_graph_relative_covariances and spg_graph_score_candidates share. n hypothetical binary edges ij[2i] -> ij[2i+1]
+// (records == nullptr: measured at the current relative pose) are checked; when `compute`, one 2D x 2D block per distinct
+// ordered pair is solved for and stays on the device, where sp_relative_kernel turns it into the results. Returns `ret`.
+int64_t relative_call(spg_graph *g, int32_t fixed_id, const int32_t *ij, int n, const double *records, bool compute, int64_t ret, double *rel,
+                      double *cov, double *d2, double *gain, double *chi2, int32_t *status, spg_cov_solve_stats *stats, const char *what) {
+    if (!g || n < 0 || (n > 0 && !ij)) return SPG_EINVAL;
+    if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    const int D = g->d;
+    const int64_t W = 2 * D;
+    std::vector<int32_t> va, vb, ca, cb, slot;
+    std::vector<int64_t> dst;
+    std::unordered_map<uint64_t, int32_t> slot_of;
+    for (int i = 0; i < n; i++) {
+        const int32_t a = ij[2 * i], b = ij[2 * i + 1];
+        const int ia = live_index(g, a), ib = live_index(g, b);
+        const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
+        if (!why && records)
+            for (int k = 0; k < g->ps; k++) if (!std::isfinite(records[(size_t)i * g->rec + k])) why = "the measurement is not finite";
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "%s: pair %d (%d, %d): %s", what, i, (int)a, (int)b, why);
+            return SPG_EINVAL;
+        }
+        if (!compute) continue;
+        auto it = slot_of.emplace(((uint64_t)(uint32_t)ia << 32) | (uint32_t)ib, (int32_t)slot_of.size());
+        if (it.second) {
+            const int32_t v[2] = {ia, ib};
+            const int64_t u = it.first->second;
+            for (int ka = 0; ka < 2; ka++)
+                for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(u * W * W + ka * D * W + kb * D); }
+        }
+        ca.push_back(ia); cb.push_back(ib); slot.push_back(it.first->second);
+    }
+    if (!compute) return ret;
+    DenseStage st;
+    spg_cov_solve_stats cs{};
+    const int64_t blocks_len = (int64_t)slot_of.size() * W * W;
+    const int staged = cov_stage(g, fixed, order, {&va, &vb}, blocks_len, nullptr, what, st);
+    if (staged < 0) return staged;
+    if (staged == 0)
+        if (int rc = spg::hip_sparse_relative(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(),
+                                              blocks_len, ca.data(), cb.data(), slot.data(), n, records, rel, cov, d2, gain, chi2, status, cs, g->ctx->err,
+                                              sizeof g->ctx->err)) return rc;
+    if (stats) *stats = cs;
+    return ret;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_relative_covariances(spg_graph *g, int32_t fixed_id, const int32_t *pairs, int n, double *rel, double *cov,
+                                                  int64_t cap, spg_cov_solve_stats *stats) {
+    const int64_t need = g ? (int64_t)std::max(n, 0) * g->d * g->d : 0;
+    return relative_call(g, fixed_id, pairs, n, nullptr, cov && cap >= need, need, rel, cov, nullptr, nullptr, nullptr, nullptr, stats,
+                         "spg_graph_relative_covariances");
+}
+
+extern "C" int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, double *d2,
+                                          double *gain, double *chi2, int32_t *status, int cap, spg_cov_solve_stats *stats) {
+    if (n > 0 && !records) return SPG_EINVAL;
+    return (int)relative_call(g, fixed_id, ij, n, n > 0 ? records : nullptr, cap >= n, n, nullptr, nullptr, d2, gain, chi2, status, stats,
+                              "spg_graph_score_candidates");
+}
+
 // ================================================================================= robust kernel
 namespace {
 // The graph's kernel into a staged graph: kind, width and, per live edge in the stage's order, whether it applies — a

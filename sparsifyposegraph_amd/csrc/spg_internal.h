@@ -119,6 +119,14 @@ int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int
 // come from the selected inverse, the others from multi-RHS column solves through the fronts.
 int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                          int64_t out_len, double *out, spg_cov_solve_stats &stats, char *err, size_t errlen);
+// Relative-pose covariances / candidate-edge scores (spg_sparse.inc: sp_relative_kernel). The sub-block lists are those of
+// hip_sparse_cov_solve for one 2D x 2D block per distinct pair (blocks_len doubles, kept on the device); candidate i uses
+// block slot[i] and the poses of vertex indices ca[i], cb[i]. rec == nullptr: rel (n x 3|7, may be nullptr) and cov
+// (n x D x D) at the current relative pose; else rec = n records (measurement + information upper triangle) and d2, gain,
+// chi2, status (n each, each may be nullptr). Host arrays throughout.
+int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                        int64_t blocks_len, const int32_t *ca, const int32_t *cb, const int32_t *slot, int n, const double *rec, double *rel,
+                        double *cov, double *d2, double *gain, double *chi2, int32_t *status, spg_cov_solve_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -484,6 +484,183 @@ __global__ __launch_bounds__(256) void sp_cov_assemble_kernel(FrontSink fs, cons
     out[b.dst + (long long)r * b.ld + c] = v;
 }
 
+// Relative-pose covariances and candidate-edge scores (spg_graph_relative_covariances / spg_graph_score_candidates) from
+// the assembled pair blocks, which stay on the device. Candidate i is a hypothetical binary edge a -> b: vertex indices
+// va[i], vb[i] (their poses, the fixed vertex included), slot[i] = its 2D x 2D block Sigma_ab in `blocks` (shared by
+// every candidate of one pair) and, when rec != nullptr, its record (measurement + upper triangle of Omega, the layout of
+// spg_graph_add_edges). With J = [Ja Jb] of se2_edge_jac / se3_edge_jac at the measurement z: P = J Sigma_ab J^T.
+//   rec == nullptr  z = the current relative pose (se2_between; Xa^-1 Xb): writes rel (t + quaternion, may be nullptr)
+//                   and P (r <= c computed, mirrored: exactly symmetric) into cov;
+//   rec != nullptr  Omega = L L^T, M = I + L^T P L = G G^T (M >= I: cannot fail for finite P), y = L^T e:
+//                   chi2 = e^T Omega e, d2 = || G^-1 y ||^2 = e^T (P + Omega^-1)^-1 e, gain = sum log G_jj = 1/2 ln det M;
+//                   Omega not finite or not PD: status 1 (SPG_CAND_INFO_NOT_PD) and three NaN, else status 0.
+// One wavefront per candidate, four per workgroup; Sigma_ab, J, J Sigma_ab, P, L and M in the wavefront's LDS slice
+// (372 doubles for D = 6). The geometry and the two D x D factorisations run on lane 0, the products over the lanes.
+struct RelArgs {
+    const double *arena;
+    const int64_t *vpo;       // per vertex index: pose offset in the arena
+    const int32_t *va, *vb, *slot;
+    const double *rec;        // n x (PS + D (D + 1) / 2) or nullptr
+    const double *blocks;     // per slot (2D)^2, row-major
+    double *rel, *cov;        // relative mode
+    double *score;            // score mode: d2[n], gain[n], chi2[n]
+    int32_t *status;
+    int n;
+};
+template <int D>
+__global__ __launch_bounds__(256) void sp_relative_kernel(RelArgs a) {
+    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3, PSZ = (D == 6) ? kIso : 3, TRI = D * (D + 1) / 2, REC = PS + TRI;
+    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
+    __shared__ double lds[4 * PER];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n;
+    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
+    double *A = T, *M = T + DD;   // score mode: P L and M reuse J Sigma_ab once P is formed
+    const bool score = a.rec != nullptr;
+    const double *rec = score && act ? a.rec + (long long)i * REC : nullptr;
+    if (act) {
+        const double *blk = a.blocks + (long long)a.slot[i] * W * W;
+        for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
+        if (lane == 0) {
+            double Xa[PSZ], Xb[PSZ], err[D];
+            load_pose<D>(a.arena, a.vpo[a.va[i]], Xa);
+            load_pose<D>(a.arena, a.vpo[a.vb[i]], Xb);
+            if (D == 6) {
+                double Z[kIso];
+                if (score) {
+                    iso_from_tq(rec, Z);
+                } else {
+                    iso_inv_mul(Xa, Xb, Z);
+                    if (a.rel) {
+                        double q[4];
+                        R_to_quat(Z, q);
+                        double *o = a.rel + (long long)i * PS;
+                        o[0] = Z[9]; o[1] = Z[10]; o[2] = Z[11]; o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+                    }
+                }
+                se3_edge_jac(Xa, Xb, Z, Ja, Jb, err);
+            } else {
+                double z[3];
+                if (score) { z[0] = rec[0]; z[1] = rec[1]; z[2] = rec[2]; }
+                else {
+                    se2_between(Xa, Xb, z);
+                    if (a.rel) { double *o = a.rel + (long long)i * PS; o[0] = z[0]; o[1] = z[1]; o[2] = z[2]; }
+                }
+                se2_edge_jac(Xa, Xb, z, Ja, Jb, err);
+            }
+#pragma unroll
+            for (int k = 0; k < D; k++) e[k] = err[k];
+        }
+    }
+    __syncthreads();
+    if (act)   // T = J Sigma_ab (D x 2D)
+        for (int k = lane; k < D * W; k += 64) {
+            const int r = k / W, c = k - r * W;
+            double s = 0;
+            for (int t = 0; t < D; t++) s += Ja[r * D + t] * S[t * W + c];
+            for (int t = 0; t < D; t++) s += Jb[r * D + t] * S[(D + t) * W + c];
+            T[k] = s;
+        }
+    __syncthreads();
+    if (act && lane < DD) {   // P = T J^T, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double s = 0;
+            for (int t = 0; t < D; t++) s += T[r * W + t] * Ja[c * D + t];
+            for (int t = 0; t < D; t++) s += T[r * W + D + t] * Jb[c * D + t];
+            P[r * D + c] = s;
+            P[c * D + r] = s;
+            if (!score) {
+                a.cov[(long long)i * DD + r * D + c] = s;
+                a.cov[(long long)i * DD + c * D + r] = s;
+            }
+        }
+    }
+    if (!score) return;
+    __shared__ int okv[4];
+    if (act && lane == 0) {   // Omega = L L^T in place (lower triangle; the upper is zeroed), chi2, y = L^T e
+        bool ok = true;
+        double chi = 0;
+        int p = PS;
+        for (int r = 0; r < D; r++)
+            for (int c = r; c < D; c++) {
+                const double v = rec[p++];
+                ok = ok && isfinite(v);
+                chi += ((r == c) ? 1.0 : 2.0) * e[r] * v * e[c];
+                L[c * D + r] = v;
+                if (c > r) L[r * D + c] = 0.0;
+            }
+        for (int j = 0; j < D && ok; j++) {
+            double d = L[j * D + j];
+            for (int k = 0; k < j; k++) d -= L[j * D + k] * L[j * D + k];
+            ok = d > 0.0 && isfinite(d);
+            if (!ok) break;
+            d = sqrt(d);
+            L[j * D + j] = d;
+            for (int r = j + 1; r < D; r++) {
+                double v = L[r * D + j];
+                for (int k = 0; k < j; k++) v -= L[r * D + k] * L[j * D + k];
+                L[r * D + j] = v / d;
+            }
+        }
+        okv[w] = ok;
+        if (ok) {
+            for (int c = 0; c < D; c++) {
+                double s = 0;
+                for (int r = c; r < D; r++) s += L[r * D + c] * e[r];
+                y[c] = s;
+            }
+            a.score[2LL * a.n + i] = chi;
+            a.status[i] = 0;
+        } else {
+            const double nan = __builtin_nan("");
+            a.score[i] = nan; a.score[(long long)a.n + i] = nan; a.score[2LL * a.n + i] = nan;
+            a.status[i] = 1;
+        }
+    }
+    __syncthreads();
+    const bool go = act && okv[w];
+    if (go && lane < DD) {   // A = P L
+        const int r = lane / D, c = lane - r * D;
+        double s = 0;
+        for (int t = c; t < D; t++) s += P[r * D + t] * L[t * D + c];
+        A[lane] = s;
+    }
+    __syncthreads();
+    if (go && lane < DD) {   // M = I + L^T A, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double s = (r == c) ? 1.0 : 0.0;
+            for (int t = r; t < D; t++) s += L[t * D + r] * A[t * D + c];
+            M[r * D + c] = s;
+            M[c * D + r] = s;
+        }
+    }
+    __syncthreads();
+    if (go && lane == 0) {   // M = G G^T in place, forward solve G x = y
+        double gain = 0, d2 = 0;
+        for (int j = 0; j < D; j++) {
+            double d = M[j * D + j];
+            for (int k = 0; k < j; k++) d -= M[j * D + k] * M[j * D + k];
+            d = sqrt(d);
+            M[j * D + j] = d;
+            gain += log(d);
+            for (int r = j + 1; r < D; r++) {
+                double v = M[r * D + j];
+                for (int k = 0; k < j; k++) v -= M[r * D + k] * M[j * D + k];
+                M[r * D + j] = v / d;
+            }
+            double x = y[j];
+            for (int k = 0; k < j; k++) x -= M[j * D + k] * y[k];
+            x /= d;
+            y[j] = x;
+            d2 += x * x;
+        }
+        a.score[i] = d2;
+        a.score[(long long)a.n + i] = gain;
+    }
+}
+
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
 // (src/utils.cpp:70-97) = 0.5 (tr(Sx^-1 Sy) + diff^T Sx^-1 diff + log det Sx - log det Sy - D), through the Cholesky
 // factors Sx = Lx Lx^T, Sy = Ly Ly^T: tr = || Lx^-1 Ly ||_F^2, Mahalanobis = || Lx^-1 diff ||^2. One lane per vertex,
@@ -1510,9 +1687,12 @@ int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int
 // sub-blocks are read from the selected inverse (bit for bit what sigma_blocks reads; SPG_COV_FORCE_SOLVE=1 sends them
 // through the solves as well); the others take one column solve per pair of vertices, shared by (a, b) and (b, a).
 // Order on the device: factorisation, column solves on the intact factor, selected inverse, one assembly launch.
-int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
-                         int64_t out_len, double *out, spg_cov_solve_stats &stats, char *err, size_t errlen) {
-    hipStream_t s = (hipStream_t)stream;
+// cov_solve_device leaves the assembled sub-blocks in dout (device, out_len doubles); `tail`, if given, launches what
+// consumes them there (it sees the staged graph; its launches are inside the selected inverse's event pair) before the
+// fronts are released. hip_sparse_cov_solve adds the copy to the host.
+using CovTail = std::function<void(hipStream_t, const GraphBufs &, const double *)>;
+static int cov_solve_device(hipStream_t s, const DenseGraphIn &in_, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                            int64_t out_len, DevBuf &dout, spg_cov_solve_stats &stats, char *err, size_t errlen, const CovTail *tail) {
     const int D = in_.D;
     const bool force = cov_force_solve();
     int rc = 0;
@@ -1553,7 +1733,7 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *v
     DenseGraphIn in = in_;
     in.pos = pos.data();
     GraphBufs gb;
-    DevBuf bad, dout, dcross, dblk;
+    DevBuf bad, dcross, dblk;
     int h_bad[2] = {0, 0};
     float ms0 = 0, ms1 = 0;
     HIPCHK(hipMalloc(&bad.p, 2 * sizeof(int)));
@@ -1582,16 +1762,69 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in_, const int32_t *v
                                (const double *)dcross.p, (double *)dout.p);
         });
     }
+    if (tail) (*tail)(s, gb, (const double *)dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(t_selinv.stop(s));
     HIPCHK(hipMemcpyAsync(h_bad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(t_selinv.ms(ms1));
     if ((rc = cov_bad_flags(h_bad, err, errlen))) return rc;
-    if (out_len > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)out_len * 8, hipMemcpyDeviceToHost));
     sp->count_into(stats.cov);
     stats.cov.device_seconds += 1e-3 * (ms0 + ms1) + cs.seconds;
     stats.columns += (int32_t)cs.cols.size(); stats.rhs_batches += cs.nbatch; stats.solve_flops += cs.flops; stats.solve_seconds += cs.seconds;
+    return 0;
+}
+
+int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                         int64_t out_len, double *out, spg_cov_solve_stats &stats, char *err, size_t errlen) {
+    DevBuf dout;
+    if (int rc = cov_solve_device((hipStream_t)stream, in, va, vb, dst, ld, nblk, out_len, dout, stats, err, errlen, nullptr)) return rc;
+    if (out_len > 0) HIPCHK(hipMemcpy(out, dout.p, (size_t)out_len * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// spg_graph_relative_covariances (rec == nullptr: rel, may be nullptr, and cov) and spg_graph_score_candidates (rec: n
+// records; d2 / gain / chi2 / status, each may be nullptr). The sub-block lists describe one 2D x 2D block per distinct
+// pair (cov_solve_device); candidate i reads block slot[i] and the poses of vertex indices ca[i], cb[i]. Only the
+// results cross to the host.
+int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                        int64_t blocks_len, const int32_t *ca, const int32_t *cb, const int32_t *slot, int n, const double *rec, double *rel,
+                        double *cov, double *d2, double *gain, double *chi2, int32_t *status, spg_cov_solve_stats &stats, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int D = in.D, PS = D == 6 ? 7 : 3, REC = PS + D * (D + 1) / 2;
+    const size_t nn = (size_t)std::max(n, 1);
+    int rc = 0;
+    DevBuf dblocks, dca, dcb, dslot, drec, drel, dcov, dscore, dstatus;
+    if ((rc = upload(dca, ca, (size_t)n, s)) || (rc = upload(dcb, cb, (size_t)n, s)) || (rc = upload(dslot, slot, (size_t)n, s)) ||
+        (rec && (rc = upload(drec, rec, (size_t)n * REC, s)))) {
+        snprintf(err, errlen, "staging the candidates failed (%d)", rc);
+        return rc;
+    }
+    if (rec) {
+        HIPCHK(hipMalloc(&dscore.p, nn * 3 * 8));
+        HIPCHK(hipMalloc(&dstatus.p, nn * sizeof(int32_t)));
+    } else {
+        HIPCHK(hipMalloc(&drel.p, nn * PS * 8));
+        HIPCHK(hipMalloc(&dcov.p, nn * D * D * 8));
+    }
+    const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *blocks) {
+        if (n <= 0) return;
+        const RelArgs ra{gb.dev.arena, gb.dev.vpo, (const int32_t *)dca.p, (const int32_t *)dcb.p, (const int32_t *)dslot.p, (const double *)drec.p, blocks,
+                         (double *)drel.p, (double *)dcov.p, (double *)dscore.p, (int32_t *)dstatus.p, n};
+        by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_relative_kernel<decltype(d)::value>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, ra); });
+    };
+    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, blocks_len, dblocks, stats, err, errlen, &tail))) return rc;
+    if (n <= 0) return 0;
+    if (rec) {
+        const double *sc = (const double *)dscore.p;
+        if (d2) HIPCHK(hipMemcpy(d2, sc, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (gain) HIPCHK(hipMemcpy(gain, sc + n, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (chi2) HIPCHK(hipMemcpy(chi2, sc + 2 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (status) HIPCHK(hipMemcpy(status, dstatus.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    } else {
+        if (rel) HIPCHK(hipMemcpy(rel, drel.p, (size_t)n * PS * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cov, dcov.p, (size_t)n * D * D * 8, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -404,6 +404,43 @@ class GraphWrapperHIP:
         self.last_covariance_stats = st.asdict()
         return out
 
+    def relativeCovariances(self, pairs, fixed_id=-1):
+        """The covariance of the relative pose Xa^-1 Xb of each pair (a, b) of distinct vertices: P = J Sigma_ab J^T with J
+        the Jacobians of the binary edge a -> b measured at the current relative pose (include/spg.h). The pair blocks stay
+        on the device. Returns (rel float64[n, 3|7], cov float64[n, D, D]); rel[i] and inv(cov[i]) are a record addEdge
+        accepts. Stats (abi.CovSolveStats) in `last_covariance_stats`."""
+        d, st = self.d, abi.CovSolveStats()
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = self.L.spg_graph_relative_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), None, None, 0, None)
+        check(min(int(n), 0), self.ctx.h, "relativeCovariances")
+        rel, cov = np.zeros((len(pr), 3 if d == 3 else 7)), np.zeros((len(pr), d, d))
+        rc = self.L.spg_graph_relative_covariances(self.h, int(fixed_id), _p(pr, C.c_int32), len(pr), _p(rel, C.c_double), _p(cov, C.c_double),
+                                                   cov.size, C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "relativeCovariances")
+        self.last_covariance_stats = st.asdict()
+        return rel, cov
+
+    def scoreCandidates(self, ij, meas, info_upper, fixed_id=-1):
+        """Scores n hypothetical binary edges ij[k, 0] -> ij[k, 1] with measurement meas[k] (3|7) and information
+        info_upper[k] (upper triangle, the layout of addEdge) against the graph, without modifying it (include/spg.h):
+        d2 = the innovation Mahalanobis distance e^T (P + Omega^-1)^-1 e (chi^2 with D degrees of freedom for an inlier),
+        gain = the information gain 1/2 ln det(I + Omega P) in nats, chi2 = e^T Omega e, status = abi.CAND_SCORED or
+        abi.CAND_INFO_NOT_PD (the three values are NaN). Returns a dict of arrays. Stats in `last_covariance_stats`."""
+        d, st = self.d, abi.CovSolveStats()
+        ij = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
+        n = len(ij)
+        rec = np.ascontiguousarray(np.concatenate([np.asarray(meas, np.float64).reshape(n, -1), np.asarray(info_upper, np.float64).reshape(n, -1)],
+                                                  axis=1))
+        if rec.shape[1] != (3 if d == 3 else 7) + d * (d + 1) // 2:
+            raise ValueError("scoreCandidates: meas must be n x (3|7) and info_upper n x D (D + 1) / 2")
+        out = {"d2": np.zeros(n), "gain": np.zeros(n), "chi2": np.zeros(n), "status": np.zeros(n, np.int32)}
+        rc = self.L.spg_graph_score_candidates(self.h, int(fixed_id), _p(ij, C.c_int32), _p(rec, C.c_double), n, _p(out["d2"], C.c_double),
+                                               _p(out["gain"], C.c_double), _p(out["chi2"], C.c_double), _p(out["status"], C.c_int32), n,
+                                               C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "scoreCandidates")
+        self.last_covariance_stats = st.asdict()
+        return out
+
     def marginalKullbackLeibler(self, other, fixed_id=-1):
         """Called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other`
         against its marginal here, for every vertex of `other` but the fixed one. Returns (ids, kld), ascending ids.

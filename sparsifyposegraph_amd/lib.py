@@ -73,6 +73,9 @@ SYMBOLS = {
     "spg_graph_marginal_kld": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int, C.POINTER(abi.CovStats)]),
     "spg_graph_pair_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
     "spg_graph_joint_marginal_covariance": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
+    "spg_graph_relative_covariances": (C.c_int64, [C.c_void_p, C.c_int32, _i32p, C.c_int, _f64p, _f64p, C.c_int64, C.POINTER(abi.CovSolveStats)]),
+    "spg_graph_score_candidates": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int, _f64p, _f64p, _f64p, _i32p, C.c_int,
+                                             C.POINTER(abi.CovSolveStats)]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "spg_ctx_set_factor_descent": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),

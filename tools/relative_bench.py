@@ -1,0 +1,70 @@
+"""One vertex against all others on the synthetic SE3 graph of the headline size: scoreCandidates (candidates measured at
+the current relative pose, Omega = the generator's info_diag), relativeCovariances, or pairCovariances of the same star
+(the 2D x 2D blocks copied to the host: what a user had to start from before). One JSON line (diagnostic).
+
+    python tools/relative_bench.py [--mode score|relative|pairs] [--poses 100000] [--ring 400] [--vertex 50000] [--runs 5]
+
+device_seconds and solve_seconds are those of spg_cov_solve_stats (HIP events: factorisation, column solves, selected
+inverse, assembly and, for score / relative, sp_relative_kernel); wall_seconds is the host clock around the whole call
+(plan, staging, uploads, the device work and the copy of the results). Medians over --runs calls after one warm-up call;
+min and max are given beside them."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sparsifyposegraph_amd import g2o_io  # noqa: E402
+from sparsifyposegraph_amd.graph import GraphWrapperHIP  # noqa: E402
+from sparsifyposegraph_amd.lib import Context  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", choices=("score", "relative", "pairs"), default="score")
+ap.add_argument("--poses", type=int, default=100000)
+ap.add_argument("--ring", type=int, default=400)
+ap.add_argument("--vertex", type=int, default=50000)
+ap.add_argument("--runs", type=int, default=5)
+args = ap.parse_args()
+
+ctx = Context(0)
+g = g2o_io.synth_sphere(args.poses, args.ring)
+hg = GraphWrapperHIP.from_dict(g, ctx=ctx)
+ids = hg.vertices()[0]
+v0 = int(ids[min(args.vertex, len(ids) - 1)])
+star = np.array([(v0, int(v)) for v in ids if int(v) != v0], np.int32)
+info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
+meas = None
+if args.mode == "score":
+    meas = hg.relativeCovariances(star)[0]          # also the warm-up of the factorisation path
+
+
+def call():
+    if args.mode == "score":
+        return sum(v.nbytes for v in hg.scoreCandidates(star, meas, info).values())
+    if args.mode == "relative":
+        rel, cov = hg.relativeCovariances(star)
+        return rel.nbytes + cov.nbytes
+    return hg.pairCovariances(star).nbytes
+
+
+call()   # warm-up: code objects, allocator
+dev, solve, wall, nbytes, s = [], [], [], 0, None
+for _ in range(args.runs):
+    t0 = time.perf_counter()
+    nbytes = call()
+    wall.append(time.perf_counter() - t0)
+    s = hg.last_covariance_stats
+    dev.append(s["device_seconds"])
+    solve.append(s["solve_seconds"])
+    print(f"{args.mode}: device {1e3 * dev[-1]:.1f} ms, wall {1e3 * wall[-1]:.1f} ms", file=sys.stderr, flush=True)
+print(json.dumps({
+    "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: vertex {v0} against all others", "mode": args.mode,
+    "candidates": len(star), "columns": s["columns"], "rhs_batches": s["rhs_batches"], "runs": args.runs,
+    "device_seconds": statistics.median(dev), "device_seconds_min": min(dev), "device_seconds_max": max(dev),
+    "solve_seconds": statistics.median(solve), "wall_seconds": statistics.median(wall), "wall_seconds_min": min(wall),
+    "wall_seconds_max": max(wall), "result_bytes": nbytes, "supernodes": s["supernodes"], "front_bytes": s["front_bytes"],
+    "factor_flops": s["factor_flops"], "selinv_flops": s["selinv_flops"], "solve_flops": s["solve_flops"]}), flush=True)
