@@ -458,6 +458,47 @@ int64_t spg_graph_relative_covariances(spg_graph *g, int32_t fixed_id, const int
 int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n,
                                double *d2, double *gain, double *chi2, int32_t *status, int cap, spg_cov_solve_stats *stats);
 
+/* ---- greedy selection of candidates by conditional information gain ------------------------------------
+ * Which k of n candidate edges are jointly most informative. `gain` above scores each candidate against the graph as it
+ * stands: ten hypotheses that close the same loop each show that loop's full gain. Here, with the J_i, e_i, L_i of
+ * spg_graph_score_candidates at the stored estimates (which do not move during the call), Sigma in the gauge of fixed_id and
+ * C_ij = J_i Sigma_(ai bi),(aj bj) J_j^T (D x D; C_ii is the P above), rounds t = 0, 1, ... run on the device:
+ *   gain_i(t) = 1/2 ln det(I + L_i^T C_ii(t) L_i)          the conditional gain given the edges chosen so far
+ *   i*        = argmax over the eligible candidates, ties to the lowest index
+ *   M = I + L*^T C**(t) L* = G G^T,  B_i,t = C_i*(t) L* G^-T,  C_ii(t+1) = C_ii(t) - B_i,t B_i,t^T,
+ *   C_ij(t) = C_ij(0) - sum_{s<t} B_i,s B_j,s^T
+ * which is Sigma' = Sigma - Sigma A^T (Omega^-1 + A Sigma A^T)^-1 A Sigma restricted to candidate space (Omega^-1 is
+ * never formed). The sum of the selected conditional gains is 1/2 (ln det H_final - ln det H_0), H_final the information
+ * after spg_graph_add_edge of the selected candidates at the same estimates.
+ * Eligible: Omega finite and positive definite (else SPG_CAND_INFO_NOT_PD) and, when max_d2 > 0, d2 <= max_d2 (else
+ * SPG_CAND_GATED). d2 is that of spg_graph_score_candidates on the graph as it stands: the gate is evaluated once, before
+ * round 0, and NOT re-evaluated as edges are selected. Selection stops after k rounds, when no candidate is eligible, or
+ * when the best conditional gain is < min_gain.
+ * The joint covariance of the m distinct non-fixed endpoints (m D x m D, each unordered pair solved once, as
+ * spg_graph_joint_marginal_covariance) and a history of min(k, n) D^2 doubles per candidate stay on the device: m D above
+ * 46 000, or a joint block and history beyond free HBM, are SPG_ECAPACITY before anything runs. a or b may be the fixed
+ * vertex, a pair may be listed many times, the graph is not modified and its robust kernel is ignored. An unknown id,
+ * a == b, a non-finite measurement, an unknown fixed vertex, k < 0 and an active stepwise marginalisation are SPG_EINVAL
+ * (the text names the pair) before the backend is touched; SPG_ESTATE without HIP. */
+enum { SPG_CAND_GATED = 2, SPG_CAND_SELECTED = 3 };
+typedef struct {
+    spg_cov_solve_stats solve;   /* the covariance part; its device_seconds covers the selection too */
+    int32_t rounds;              /* rounds run = candidates selected */
+    int32_t endpoints;           /* m */
+    double select_seconds;       /* HIP-event time of the selection alone: initial gains, the rounds, final gains */
+} spg_select_stats;
+/* ij, records, n: as spg_graph_score_candidates. selected, cond_gain: min(k, n) entries in order of selection, cond_gain[t]
+ * = the conditional gain of selected[t] when it was chosen; entries beyond the return value are -1 / NaN. final_gain (n, may
+ * be NULL): the conditional gain after the last round, NaN for selected, gated and not-PD candidates. status (n, may be
+ * NULL): SPG_CAND_SCORED (eligible, not selected), _INFO_NOT_PD, _GATED or _SELECTED. A candidate whose downdated C_ii
+ * rounding has made indefinite gets a NaN gain: it is never picked and stays SPG_CAND_SCORED with a NaN final_gain. The
+ * free-HBM check covers the joint block and the histories and runs before anything is allocated or launched; the factor's
+ * fronts are checked against what is then left (SPG_ECAPACITY as in the covariance calls). Returns the number selected; with
+ * cap < min(k, n) (or selected / cond_gain NULL) returns min(k, n) and writes nothing. n = 0 or k = 0 returns 0. */
+int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k,
+                                double min_gain, double max_d2, int32_t *selected, double *cond_gain, int cap,
+                                double *final_gain, int32_t *status, spg_select_stats *stats);
+
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the
  * smallest id), g2o's Levenberg-Marquardt for up to `iterations` iterations (the reference uses 50),

@@ -562,6 +562,33 @@ public:
         for (int i = 0; i < n; i++) out.push_back({d2[i], gain[i], chi2[i], (int)status[i]});
         return out;
     }
+    // Greedy choice of up to k candidates by conditional information gain (include/spg.h: spg_graph_select_candidates):
+    // (index into cands, its gain given the ones chosen before it), in order of selection. max_d2 > 0 gates on the d2 of
+    // scoreCandidates, evaluated once on the graph as it stands. status, if given: SPG_CAND_* per candidate.
+    std::vector<std::pair<int, double>> selectCandidates(const std::vector<Candidate> &cands, int k, double min_gain = 0.0, double max_d2 = 0.0,
+                                                         int fixed_id = -1, std::vector<int> *status = nullptr, spg_select_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g), n = (int)cands.size();
+        std::vector<int32_t> ij;
+        std::vector<double> rec;
+        for (const Candidate &c : cands) {
+            if (c.information.rows() != d || c.information.cols() != d) throw std::runtime_error("selectCandidates: information must be d x d");
+            const VectorXd &z = c.measurement;
+            if ((int)z.size() != (d == 3 ? 3 : 7)) throw std::runtime_error("selectCandidates: the measurement does not match the graph's pose dimension");
+            ij.push_back(c.from); ij.push_back(c.to);
+            rec.insert(rec.end(), z.begin(), z.end());
+            for (int i = 0; i < d; i++) for (int j = i; j < d; j++) rec.push_back(c.information(i, j));
+        }
+        const int cap = std::max(std::min(k, n), 0);
+        std::vector<int32_t> sel((size_t)std::max(cap, 1)), st((size_t)std::max(n, 1));
+        std::vector<double> gain(sel.size());
+        const int r = spg_graph_select_candidates(_g, fixed_id, ij.data(), rec.data(), n, k, min_gain, max_d2, sel.data(), gain.data(), cap, nullptr,
+                                                  st.data(), stats);
+        check(std::min(r, 0), "selectCandidates");
+        std::vector<std::pair<int, double>> out;
+        for (int i = 0; i < r; i++) out.emplace_back((int)sel[i], gain[i]);
+        if (status) status->assign(st.begin(), st.begin() + n);
+        return out;
+    }
     // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
     // its marginal here, every vertex of `other` but the fixed one; ids ascending
     std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {

@@ -104,6 +104,18 @@ class CovSolveStats(C.Structure):
 
 # SPG_CAND_* (include/spg.h): status of a candidate of spg_graph_score_candidates
 CAND_SCORED, CAND_INFO_NOT_PD = 0, 1
+# further values of spg_graph_select_candidates
+CAND_GATED, CAND_SELECTED = 2, 3
+
+
+class SelectStats(C.Structure):
+    """spg_select_stats (include/spg.h)"""
+    _fields_ = [("solve", CovSolveStats), ("rounds", C.c_int32), ("endpoints", C.c_int32), ("select_seconds", C.c_double)]
+
+    def asdict(self):
+        d = self.solve.asdict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_[1:]})
+        return d
 
 
 class OptimizeStats(C.Structure):

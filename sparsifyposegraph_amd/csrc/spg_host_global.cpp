@@ -461,6 +461,19 @@ extern "C" int64_t spg_graph_joint_marginal_covariance(spg_graph *g, int32_t fix
 
 // ================================================================================= relative covariances, candidate scores
 namespace {
+// Candidate i of relative_call / select_call, ij[2i] -> ij[2i+1] with record i of `records` (may be nullptr): its vertex
+// indices, or SPG_EINVAL with the pair named.
+int check_pair(spg_graph *g, const char *what, int i, const int32_t *ij, const double *records, int &ia, int &ib) {
+    const int32_t a = ij[2 * i], b = ij[2 * i + 1];
+    ia = live_index(g, a);
+    ib = live_index(g, b);
+    const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
+    if (!why && records)
+        for (int k = 0; k < g->ps; k++) if (!std::isfinite(records[(size_t)i * g->rec + k])) why = "the measurement is not finite";
+    if (!why) return 0;
+    snprintf(g->ctx->err, sizeof g->ctx->err, "%s: pair %d (%d, %d): %s", what, i, (int)a, (int)b, why);
+    return SPG_EINVAL;
+}
 // What spg_graph_relative_covariances and spg_graph_score_candidates share. n hypothetical binary edges ij[2i] -> ij[2i+1]
 // (records == nullptr: measured at the current relative pose) are checked; when `compute`, one 2D x 2D block per distinct
 // ordered pair is solved for and stays on the device, where sp_relative_kernel turns it into the results. Returns `ret`.
@@ -477,15 +490,8 @@ int64_t relative_call(spg_graph *g, int32_t fixed_id, const int32_t *ij, int n, 
     std::vector<int64_t> dst;
     std::unordered_map<uint64_t, int32_t> slot_of;
     for (int i = 0; i < n; i++) {
-        const int32_t a = ij[2 * i], b = ij[2 * i + 1];
-        const int ia = live_index(g, a), ib = live_index(g, b);
-        const char *why = (ia < 0 || ib < 0) ? "a vertex is not in the graph" : (a == b) ? "the two vertices are the same" : nullptr;
-        if (!why && records)
-            for (int k = 0; k < g->ps; k++) if (!std::isfinite(records[(size_t)i * g->rec + k])) why = "the measurement is not finite";
-        if (why) {
-            snprintf(g->ctx->err, sizeof g->ctx->err, "%s: pair %d (%d, %d): %s", what, i, (int)a, (int)b, why);
-            return SPG_EINVAL;
-        }
+        int ia, ib;
+        if (int rc = check_pair(g, what, i, ij, records, ia, ib)) return rc;
         if (!compute) continue;
         auto it = slot_of.emplace(((uint64_t)(uint32_t)ia << 32) | (uint32_t)ib, (int32_t)slot_of.size());
         if (it.second) {
@@ -523,6 +529,71 @@ extern "C" int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const 
     if (n > 0 && !records) return SPG_EINVAL;
     return (int)relative_call(g, fixed_id, ij, n, n > 0 ? records : nullptr, cap >= n, n, nullptr, nullptr, d2, gain, chi2, status, stats,
                               "spg_graph_score_candidates");
+}
+
+// ================================================================================= greedy candidate selection
+namespace {
+// spg_graph_select_candidates: the checks of relative_call, then the endpoint set S (distinct non-fixed endpoints in
+// first-appearance order), the sub-block list of its m x m joint covariance as spg_graph_joint_marginal_covariance builds
+// it, and per candidate the slots of its endpoints in S (-1 = the fixed vertex).
+int select_call(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k, double min_gain, double max_d2,
+                int32_t *selected, double *cond_gain, int cap, double *final_gain, int32_t *status, spg_select_stats *stats) {
+    const char *what = "spg_graph_select_candidates";
+    if (!g || n < 0 || (n > 0 && (!ij || !records))) return SPG_EINVAL;
+    if (k < 0) return set_err(g->ctx, SPG_EINVAL, "%s: k is negative", what);
+    if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    const int D = g->d;
+    std::vector<int32_t> S, ca((size_t)n), cb((size_t)n), sa((size_t)n), sb((size_t)n);
+    std::unordered_map<int32_t, int32_t> slot_of;
+    for (int i = 0; i < n; i++) {
+        int ia, ib;
+        if (int rc = check_pair(g, what, i, ij, records, ia, ib)) return rc;
+        ca[i] = ia; cb[i] = ib;
+        const int32_t v[2] = {ia, ib};
+        int32_t sl[2];
+        for (int e = 0; e < 2; e++) {
+            if (v[e] == fixed) { sl[e] = -1; continue; }
+            auto it = slot_of.emplace(v[e], (int32_t)S.size());
+            if (it.second) S.push_back(v[e]);
+            sl[e] = it.first->second;
+        }
+        sa[i] = sl[0]; sb[i] = sl[1];
+    }
+    const int kk = std::min(k, n);
+    if (kk == 0) return 0;
+    const int64_t m = (int64_t)S.size(), W = m * D, need = W * W;
+    if (W > 46000) {
+        snprintf(g->ctx->err, sizeof g->ctx->err, "%s: %lld distinct endpoints, limited to 46k variables, the bound of spg_graph_joint_marginal_covariance",
+                 what, (long long)m);
+        return SPG_ECAPACITY;
+    }
+    if (!selected || !cond_gain || cap < kk) return kk;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
+    for (int64_t a = 0; a < m; a++)
+        for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
+    DenseStage st;
+    spg_select_stats ss{};
+    ss.endpoints = (int32_t)m;
+    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
+    if (staged < 0) return staged;
+    int nsel = 0;
+    if (int rc = spg::hip_sparse_select(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
+                                        ca.data(), cb.data(), sa.data(), sb.data(), n, records, kk, min_gain, max_d2, selected, cond_gain, final_gain,
+                                        status, &nsel, ss, g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (stats) *stats = ss;
+    return nsel;
+}
+}  // namespace
+
+extern "C" int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k, double min_gain,
+                                           double max_d2, int32_t *selected, double *cond_gain, int cap, double *final_gain, int32_t *status,
+                                           spg_select_stats *stats) {
+    return select_call(g, fixed_id, ij, records, n, k, min_gain, max_d2, selected, cond_gain, cap, final_gain, status, stats);
 }
 
 // ================================================================================= robust kernel

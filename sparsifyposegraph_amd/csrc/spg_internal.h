@@ -127,6 +127,14 @@ int hip_sparse_cov_solve(void *stream, const DenseGraphIn &in, const int32_t *va
 int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                         int64_t blocks_len, const int32_t *ca, const int32_t *cb, const int32_t *slot, int n, const double *rec, double *rel,
                         double *cov, double *d2, double *gain, double *chi2, int32_t *status, spg_cov_solve_stats &stats, char *err, size_t errlen);
+// Greedy candidate selection (spg_sparse.inc: sp_select_*_kernel). The sub-block lists are those of hip_sparse_cov_solve
+// for the m D x m D joint covariance of the candidates' distinct non-fixed endpoints (joint_len doubles, row stride ld, kept
+// on the device); candidate i has the poses of vertex indices ca[i], cb[i] and the endpoint slots sa[i], sb[i] in that
+// block (-1 = the fixed vertex). n, kk >= 1. selected, cond_gain: kk entries; final_gain, status: n each, may be nullptr.
+int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                      int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
+                      double min_gain, double max_d2, int32_t *selected, double *cond_gain, double *final_gain, int32_t *status, int *nsel,
+                      spg_select_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

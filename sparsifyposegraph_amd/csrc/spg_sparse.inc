@@ -661,6 +661,399 @@ __global__ __launch_bounds__(256) void sp_relative_kernel(RelArgs a) {
     }
 }
 
+// The steps of sp_relative_kernel as functions, for the selection kernels below. Each is one wavefront's work between two
+// barriers over its own LDS slice; "lane 0" steps are called by that lane alone. sp_relative_kernel itself keeps its own
+// text: built from these functions (or as one body shared with sp_select_init_kernel) its SE3 results moved in the last
+// bits (P by up to 2.7e-12 relative: other fused multiply-adds in the inlined geometry), and the existing calls return the
+// bits they returned before. A change to the arithmetic of one has to be made in the other.
+// lane 0: the poses of vertices va, vb, the measurement (rec, or the current relative pose, written to rel if given), the
+// Jacobians and the error
+template <int D>
+__device__ __forceinline__ void rel_geometry(const double *arena, const int64_t *vpo, int32_t va, int32_t vb, const double *rec, double *rel, double *Ja,
+                                             double *Jb, double *e) {
+    constexpr int PSZ = (D == 6) ? kIso : 3;
+    double Xa[PSZ], Xb[PSZ], err[D];
+    load_pose<D>(arena, vpo[va], Xa);
+    load_pose<D>(arena, vpo[vb], Xb);
+    if (D == 6) {
+        double Z[kIso];
+        if (rec) {
+            iso_from_tq(rec, Z);
+        } else {
+            iso_inv_mul(Xa, Xb, Z);
+            if (rel) {
+                double q[4];
+                R_to_quat(Z, q);
+                rel[0] = Z[9]; rel[1] = Z[10]; rel[2] = Z[11]; rel[3] = q[0]; rel[4] = q[1]; rel[5] = q[2]; rel[6] = q[3];
+            }
+        }
+        se3_edge_jac(Xa, Xb, Z, Ja, Jb, err);
+    } else {
+        double z[3];
+        if (rec) { z[0] = rec[0]; z[1] = rec[1]; z[2] = rec[2]; }
+        else {
+            se2_between(Xa, Xb, z);
+            if (rel) { rel[0] = z[0]; rel[1] = z[1]; rel[2] = z[2]; }
+        }
+        se2_edge_jac(Xa, Xb, z, Ja, Jb, err);
+    }
+#pragma unroll
+    for (int k = 0; k < D; k++) e[k] = err[k];
+}
+// T = [Ja Jb] S (D x 2D), S a 2D x 2D block
+template <int D>
+__device__ __forceinline__ void rel_J_sigma(int lane, const double *Ja, const double *Jb, const double *S, double *T) {
+    constexpr int W = 2 * D;
+    for (int k = lane; k < D * W; k += 64) {
+        const int r = k / W, c = k - r * W;
+        double s = 0;
+        for (int t = 0; t < D; t++) s += Ja[r * D + t] * S[t * W + c];
+        for (int t = 0; t < D; t++) s += Jb[r * D + t] * S[(D + t) * W + c];
+        T[k] = s;
+    }
+}
+// lanes < D^2: P = T [Ja Jb]^T, r <= c, mirrored; also into cov if given
+template <int D>
+__device__ __forceinline__ void rel_P(int lane, const double *T, const double *Ja, const double *Jb, double *P, double *cov) {
+    constexpr int W = 2 * D;
+    const int r = lane / D, c = lane - r * D;
+    if (r <= c) {
+        double s = 0;
+        for (int t = 0; t < D; t++) s += T[r * W + t] * Ja[c * D + t];
+        for (int t = 0; t < D; t++) s += T[r * W + D + t] * Jb[c * D + t];
+        P[r * D + c] = s;
+        P[c * D + r] = s;
+        if (cov) {
+            cov[r * D + c] = s;
+            cov[c * D + r] = s;
+        }
+    }
+}
+// lane 0: Omega (info: its upper triangle) = L L^T in place (lower triangle; the upper is zeroed), chi = e^T Omega e and,
+// when Omega is finite and positive definite (the return value), y = L^T e
+template <int D>
+__device__ __forceinline__ bool rel_omega(const double *info, const double *e, double *L, double *y, double &chi_out) {
+    bool ok = true;
+    double chi = 0;
+    int p = 0;
+    for (int r = 0; r < D; r++)
+        for (int c = r; c < D; c++) {
+            const double v = info[p++];
+            ok = ok && isfinite(v);
+            chi += ((r == c) ? 1.0 : 2.0) * e[r] * v * e[c];
+            L[c * D + r] = v;
+            if (c > r) L[r * D + c] = 0.0;
+        }
+    for (int j = 0; j < D && ok; j++) {
+        double d = L[j * D + j];
+        for (int k = 0; k < j; k++) d -= L[j * D + k] * L[j * D + k];
+        ok = d > 0.0 && isfinite(d);
+        if (!ok) break;
+        d = sqrt(d);
+        L[j * D + j] = d;
+        for (int r = j + 1; r < D; r++) {
+            double v = L[r * D + j];
+            for (int k = 0; k < j; k++) v -= L[r * D + k] * L[j * D + k];
+            L[r * D + j] = v / d;
+        }
+    }
+    if (ok)
+        for (int c = 0; c < D; c++) {
+            double s = 0;
+            for (int r = c; r < D; r++) s += L[r * D + c] * e[r];
+            y[c] = s;
+        }
+    chi_out = chi;
+    return ok;
+}
+// lanes < D^2: A = P L (L lower triangular)
+template <int D>
+__device__ __forceinline__ void rel_PL(int lane, const double *P, const double *L, double *A) {
+    const int r = lane / D, c = lane - r * D;
+    double s = 0;
+    for (int t = c; t < D; t++) s += P[r * D + t] * L[t * D + c];
+    A[lane] = s;
+}
+// lanes < D^2: M = I + L^T A, r <= c, mirrored
+template <int D>
+__device__ __forceinline__ void rel_M(int lane, const double *L, const double *A, double *M) {
+    const int r = lane / D, c = lane - r * D;
+    if (r <= c) {
+        double s = (r == c) ? 1.0 : 0.0;
+        for (int t = r; t < D; t++) s += L[t * D + r] * A[t * D + c];
+        M[r * D + c] = s;
+        M[c * D + r] = s;
+    }
+}
+// lane 0: M = G G^T in place (lower triangle) with the forward solve G x = y interleaved (x replaces y):
+// gain = sum log G_jj, d2 = || x ||^2
+template <int D>
+__device__ __forceinline__ void rel_chol_M(double *M, double *y, double &gain_out, double &d2_out) {
+    double gain = 0, d2 = 0;
+    for (int j = 0; j < D; j++) {
+        double d = M[j * D + j];
+        for (int k = 0; k < j; k++) d -= M[j * D + k] * M[j * D + k];
+        d = sqrt(d);
+        M[j * D + j] = d;
+        gain += log(d);
+        for (int r = j + 1; r < D; r++) {
+            double v = M[r * D + j];
+            for (int k = 0; k < j; k++) v -= M[r * D + k] * M[j * D + k];
+            M[r * D + j] = v / d;
+        }
+        double x = y[j];
+        for (int k = 0; k < j; k++) x -= M[j * D + k] * y[k];
+        x /= d;
+        y[j] = x;
+        d2 += x * x;
+    }
+    gain_out = gain;
+    d2_out = d2;
+}
+
+// Greedy selection of candidate edges by conditional information gain (spg_graph_select_candidates, DESIGN 5g-S). The
+// joint covariance of the m distinct non-fixed endpoints (m D x m D, row-major) stays on the device; candidate i is the
+// edge va[i] -> vb[i] (vertex indices: the poses) whose endpoints sit at block slots sa[i], sb[i] of the joint block
+// (-1 = the fixed vertex: zero blocks). With C_ij = J_i Sigma_(ai bi),(aj bj) J_j^T, round t picks i* = argmax of
+// gain_i = 1/2 ln det(I + L_i^T C_ii L_i) over state 0 (ties: the lowest index) and conditions on it: M = I + L*^T C** L*
+// = G G^T, B_i,t = C_i*(t) L* G^-T with C_i*(t) = C_i*(0) - sum_{s<t} B_i,s B_*,s^T, C_ii -= B_i,t B_i,t^T. Per candidate
+// in HBM: Ja Jb, L, C_ii(t), the history B_i,0..t (kk D^2), gain, d2 and the state (the SPG_CAND_* value it reports).
+struct SelArgs {
+    const double *arena;
+    const int64_t *vpo;
+    const int32_t *va, *vb, *sa, *sb;
+    const double *rec;        // n x (PS + D (D + 1) / 2)
+    const double *joint;      // m D x m D, row stride ld
+    long long ld;
+    double *J, *L, *C;        // n x 2 D^2, n x D^2, n x D^2
+    double *hist;             // n x kk x D^2
+    double *gain, *d2;        // n each
+    int32_t *state;           // n
+    double *pg;               // argmax partials: np gains, np indices
+    int32_t *pi;
+    int32_t *ctl;             // [0] rounds done = number selected, [1] the stop rule has fired, [2] i* of the current round
+    double *pubC;             // D^2: C_**(t) as it was when i* was picked
+    int32_t *sel;             // kk: the choices in order
+    double *cg;               // kk: their conditional gains
+    double *final_gain;       // n
+    int n, kk, np;
+    double min_gain, max_d2;
+};
+// the 2D x 2D block [[S(ra, ca), S(ra, cb)], [S(rb, ca), S(rb, cb)]] of the joint block into LDS
+template <int D>
+__device__ __forceinline__ void sel_load_sigma(int lane, const double *joint, long long ld, int ra, int rb, int ca, int cb, double *S) {
+    constexpr int W = 2 * D;
+    for (int k = lane; k < W * W; k += 64) {
+        const int r = k / W, c = k - r * W;
+        const int br = r < D ? ra : rb, bc = c < D ? ca : cb;
+        const int rr = r < D ? r : r - D, cc = c < D ? c : c - D;
+        S[k] = (br < 0 || bc < 0) ? 0.0 : joint[((long long)br * D + rr) * ld + (long long)bc * D + cc];
+    }
+}
+// One wavefront per candidate, four per workgroup, the LDS slice of sp_relative_kernel: J, L, C_ii(0) = P, gain_i(0), d2
+// and the state (Omega not PD: 1; max_d2 > 0 and d2 > max_d2: 2; else 0).
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_init_kernel(SelArgs a) {
+    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3, TRI = D * (D + 1) / 2, REC = PS + TRI;
+    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n;
+    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
+    double *A = T, *M = T + DD;
+    const double *rec = act ? a.rec + (long long)i * REC : nullptr;
+    if (act) {
+        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.va[i], a.vb[i], rec, nullptr, Ja, Jb, e);
+    }
+    __syncthreads();
+    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
+    __syncthreads();
+    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
+    if (act && lane == 0) {
+        double chi;
+        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
+    }
+    __syncthreads();
+    const bool go = act && okv[w];
+    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
+    __syncthreads();
+    if (go && lane < DD) rel_M<D>(lane, L, A, M);
+    __syncthreads();
+    if (act && lane == 0) {
+        double gain = __builtin_nan(""), d2 = gain;
+        int st = 1;
+        if (go) {
+            rel_chol_M<D>(M, y, gain, d2);
+            st = (a.max_d2 > 0.0 && !(d2 <= a.max_d2)) ? 2 : 0;
+        }
+        a.gain[i] = gain;
+        a.d2[i] = d2;
+        a.state[i] = st;
+    }
+    if (act && lane < DD) {
+        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
+        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
+        a.L[(long long)i * DD + lane] = L[lane];
+        a.C[(long long)i * DD + lane] = P[lane];
+    }
+}
+// (gain descending, index ascending): the order of the argmax, independent of the grid
+__device__ __forceinline__ bool sel_better(double ga, int ia, double gb, int ib) { return ga > gb || (ga == gb && ia < ib); }
+__device__ __forceinline__ void sel_reduce(double &g, int &i, double *sg, int *si) {
+    const int t = threadIdx.x;
+    sg[t] = g; si[t] = i;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h && sel_better(sg[t + h], si[t + h], sg[t], si[t])) { sg[t] = sg[t + h]; si[t] = si[t + h]; }
+        __syncthreads();
+    }
+    g = sg[0]; i = si[0];
+}
+// Stage 1 (pick == 0, np workgroups): the best (gain, index) of the candidates in state 0 per workgroup into pg / pi.
+// Stage 2 (pick == 1, one workgroup): the best of the partials; none, or a gain below min_gain: ctl[1] = 1. Else i* is
+// appended to sel / cg, marked selected, and its C_ii is published for the round kernel.
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_argmax_kernel(SelArgs a, int pick) {
+    constexpr int DD = D * D;
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    __shared__ int chosen;
+    const int stop = a.ctl[1];   // read by every thread before the first barrier; written after it by thread 0 alone
+    double g = -__builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop) {
+        if (!pick) {
+            for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256)
+                if (a.state[i] == 0 && sel_better(a.gain[i], i, g, bi)) { g = a.gain[i]; bi = i; }
+        } else {
+            for (int p = threadIdx.x; p < a.np; p += 256)
+                if (sel_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+        }
+    }
+    sel_reduce(g, bi, sg, si);
+    if (stop) return;
+    if (!pick) {
+        if (threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
+        return;
+    }
+    if (threadIdx.x == 0) {
+        if (bi == 0x7fffffff || g < a.min_gain) {
+            a.ctl[1] = 1;
+            chosen = -1;
+        } else {
+            const int c = a.ctl[0];
+            a.sel[c] = bi;
+            a.cg[c] = g;
+            a.ctl[0] = c + 1;
+            a.ctl[2] = bi;
+            a.state[bi] = 3;
+            chosen = bi;
+        }
+    }
+    __syncthreads();
+    if (chosen >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)chosen * DD + threadIdx.x];
+}
+// Conditions every candidate still in state 0, and i* itself, on i* (read from ctl). One wavefront per candidate.
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_round_kernel(SelArgs a) {
+    constexpr int W = 2 * D, DD = D * D;
+    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
+    __shared__ double lds[4 * PER];
+    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
+    const int s = a.ctl[2], t = a.ctl[0] - 1;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
+    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
+           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD, *y = Ci + DD;
+    if (act) {
+        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
+        for (int k = lane; k < 2 * DD; k += 64) {
+            Ji[k] = a.J[(long long)i * 2 * DD + k];
+            Js[k] = a.J[(long long)s * 2 * DD + k];
+        }
+        if (lane < DD) {
+            Ls[lane] = a.L[(long long)s * DD + lane];
+            Ms[lane] = a.pubC[lane];
+            Li[lane] = a.L[(long long)i * DD + lane];
+            Ci[lane] = a.C[(long long)i * DD + lane];
+        }
+        if (lane < D) y[lane] = 0.0;
+    }
+    __syncthreads();
+    if (act) {
+        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
+        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        rel_M<D>(lane, Ls, As, Ms);                    // M = I + L*^T C** L*
+        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
+        double x = 0;
+        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
+        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
+        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
+        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
+            x -= d;
+        }
+        X[lane] = x;
+    }
+    __syncthreads();
+    if (act && lane == 0) {
+        double g, d2;
+        rel_chol_M<D>(Ms, y, g, d2);                   // G in the lower triangle of Ms
+    }
+    __syncthreads();
+    if (act && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
+        const int r = lane;
+        for (int j = 0; j < D; j++) {
+            double v = (j <= r) ? Ls[r * D + j] : 0.0;
+            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
+            K[r * D + j] = v / Ms[j * D + j];
+        }
+    }
+    __syncthreads();
+    if (act && lane < DD) {                            // B_i,t = X K, appended to the history
+        const int r = lane / D, c = lane - r * D;
+        double v = 0;
+        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
+        B[lane] = v;
+        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
+    }
+    __syncthreads();
+    if (act && lane < DD) {                            // C_ii -= B B^T, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
+            const double v = Ci[r * D + c] - d;
+            Ci[r * D + c] = v;
+            Ci[c * D + r] = v;
+        }
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        a.C[(long long)i * DD + lane] = Ci[lane];
+        if (go) rel_PL<D>(lane, Ci, Li, As);
+    }
+    __syncthreads();
+    if (go && lane < DD) rel_M<D>(lane, Li, As, Ms);
+    __syncthreads();
+    if (go && lane == 0) {
+        double g, d2;
+        rel_chol_M<D>(Ms, y, g, d2);
+        a.gain[i] = g;
+    }
+}
+// final_gain: the conditional gain after the last round of every candidate still in state 0, NaN for the others
+__global__ __launch_bounds__(256) void sp_select_gather_kernel(SelArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n) a.final_gain[i] = a.state[i] == 0 ? a.gain[i] : __builtin_nan("");
+}
+
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
 // (src/utils.cpp:70-97) = 0.5 (tr(Sx^-1 Sy) + diff^T Sx^-1 diff + log det Sx - log det Sy - D), through the Cholesky
 // factors Sx = Lx Lx^T, Sy = Ly Ly^T: tr = || Lx^-1 Ly ||_F^2, Mahalanobis = || Lx^-1 diff ||^2. One lane per vertex,
@@ -1825,6 +2218,94 @@ int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va,
         if (rel) HIPCHK(hipMemcpy(rel, drel.p, (size_t)n * PS * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(cov, dcov.p, (size_t)n * D * D * 8, hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// spg_graph_select_candidates: the sub-block lists describe the m D x m D joint covariance of the candidates' endpoints
+// (joint_len doubles, row stride ld, kept on the device); candidate i has the poses of vertex indices ca[i], cb[i] and
+// the endpoint slots sa[i], sb[i] (-1: the fixed vertex). The tail enqueues init, kk x (argmax, argmax, round) and the
+// gather without a synchronisation; the stop rules are device words the later launches return on. selected / cond_gain:
+// kk entries (the tail beyond *nsel is -1 / NaN), final_gain / status: n each, may be nullptr. Host arrays throughout.
+int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                      int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
+                      double min_gain, double max_d2, int32_t *selected, double *cond_gain, double *final_gain, int32_t *status, int *nsel,
+                      spg_select_stats &stats, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int D = in.D, DD = D * D, PS = D == 6 ? 7 : 3, REC = PS + D * (D + 1) / 2;
+    const int np = std::min((n + 255) / 256, 256);
+    int rc = 0;
+    {
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
+        if (bytes + (double)(1ull << 30) > (double)free_b) {
+            snprintf(err, errlen, "candidate selection needs %.1f GB for the joint covariance of the endpoints and the histories, %.1f GB are free",
+                     bytes * 1e-9, free_b * 1e-9);
+            return SPG_ECAPACITY;
+        }
+    }
+    DevBuf djoint, dca, dcb, dsa, dsb, drec, dJ, dL, dC, dhist, dgain, dd2, dstate, dpg, dpi, dctl, dpub, dsel, dcg, dfinal;
+    if ((rc = upload(dca, ca, (size_t)n, s)) || (rc = upload(dcb, cb, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) ||
+        (rc = upload(dsb, sb, (size_t)n, s)) || (rc = upload(drec, rec, (size_t)n * REC, s))) {
+        snprintf(err, errlen, "staging the candidates failed (%d)", rc);
+        return rc;
+    }
+    HIPCHK(hipMalloc(&dJ.p, (size_t)n * 2 * DD * 8));
+    HIPCHK(hipMalloc(&dL.p, (size_t)n * DD * 8));
+    HIPCHK(hipMalloc(&dC.p, (size_t)n * DD * 8));
+    HIPCHK(hipMalloc(&dhist.p, (size_t)n * kk * DD * 8));
+    HIPCHK(hipMalloc(&dgain.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dd2.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dstate.p, (size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dpg.p, (size_t)np * 8));
+    HIPCHK(hipMalloc(&dpi.p, (size_t)np * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dctl.p, 4 * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dpub.p, (size_t)DD * 8));
+    HIPCHK(hipMalloc(&dsel.p, (size_t)kk * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dcg.p, (size_t)kk * 8));
+    HIPCHK(hipMalloc(&dfinal.p, (size_t)n * 8));
+    HIPCHK(hipMemsetAsync(dctl.p, 0, 4 * sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(dsel.p, 0xff, (size_t)kk * sizeof(int32_t), s));   // -1
+    HIPCHK(hipMemsetAsync(dcg.p, 0xff, (size_t)kk * 8, s));                  // NaN
+    EventTimer t_select;
+    hipError_t tail_err = hipSuccess;
+    const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
+        SelArgs a{};
+        a.arena = gb.dev.arena; a.vpo = gb.dev.vpo;
+        a.va = (const int32_t *)dca.p; a.vb = (const int32_t *)dcb.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
+        a.rec = (const double *)drec.p; a.joint = joint; a.ld = ld;
+        a.J = (double *)dJ.p; a.L = (double *)dL.p; a.C = (double *)dC.p; a.hist = (double *)dhist.p;
+        a.gain = (double *)dgain.p; a.d2 = (double *)dd2.p; a.state = (int32_t *)dstate.p;
+        a.pg = (double *)dpg.p; a.pi = (int32_t *)dpi.p; a.ctl = (int32_t *)dctl.p; a.pubC = (double *)dpub.p;
+        a.sel = (int32_t *)dsel.p; a.cg = (double *)dcg.p; a.final_gain = (double *)dfinal.p;
+        a.n = n; a.kk = kk; a.np = np; a.min_gain = min_gain; a.max_d2 = max_d2;
+        const dim3 per_cand((unsigned)((n + 3) / 4));
+        tail_err = t_select.start(st);
+        by_dim(D, [&](auto d) {
+            constexpr int DV = decltype(d)::value;
+            hipLaunchKernelGGL((sp_select_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
+            for (int t = 0; t < kk; t++) {
+                hipLaunchKernelGGL((sp_select_argmax_kernel<DV>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
+                hipLaunchKernelGGL((sp_select_argmax_kernel<DV>), dim3(1), dim3(256), 0, st, a, 1);
+                hipLaunchKernelGGL((sp_select_round_kernel<DV>), per_cand, dim3(256), 0, st, a);
+            }
+        });
+        hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        if (tail_err == hipSuccess) tail_err = t_select.stop(st);
+    };
+    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail))) return rc;
+    HIPCHK(tail_err);
+    float ms = 0;
+    HIPCHK(t_select.ms(ms));
+    int32_t ctl[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(ctl, dctl.p, sizeof ctl, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(selected, dsel.p, (size_t)kk * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cond_gain, dcg.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
+    if (final_gain) HIPCHK(hipMemcpy(final_gain, dfinal.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dstate.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *nsel = ctl[0];
+    stats.rounds = ctl[0];
+    stats.select_seconds = 1e-3 * ms;
     return 0;
 }
 

@@ -441,6 +441,33 @@ class GraphWrapperHIP:
         self.last_covariance_stats = st.asdict()
         return out
 
+    def selectCandidates(self, ij, meas, info_upper, k, min_gain=0.0, max_d2=0.0, fixed_id=-1):
+        """Greedy choice of up to k of the n candidates of scoreCandidates' layout by conditional information gain
+        (include/spg.h: spg_graph_select_candidates): each round takes the candidate with the largest gain given the ones
+        already chosen (ties: the lowest index), on the device, without modifying the graph. max_d2 > 0 gates on the d2 of
+        the graph as it stands (evaluated once); selection stops early when the best gain is < min_gain or nothing is
+        eligible. Returns a dict: selected int32[r] (indices into the list, in order), cond_gain float64[r], final_gain
+        float64[n] (NaN for selected, gated and not-PD candidates), status int32[n] (abi.CAND_*). Stats
+        (abi.SelectStats) in `last_covariance_stats`."""
+        d, st = self.d, abi.SelectStats()
+        ij = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
+        n = len(ij)
+        ps, tri = (3 if d == 3 else 7), d * (d + 1) // 2
+        meas, info_upper = np.asarray(meas, np.float64), np.asarray(info_upper, np.float64)
+        if meas.size != n * ps or info_upper.size != n * tri:
+            raise ValueError("selectCandidates: meas must be n x (3|7) and info_upper n x D (D + 1) / 2")
+        rec = np.ascontiguousarray(np.concatenate([meas.reshape(n, ps), info_upper.reshape(n, tri)], axis=1))
+        cap = max(min(int(k), n), 0)
+        sel, cg = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), np.nan)
+        out = {"final_gain": np.full(n, np.nan), "status": np.zeros(n, np.int32)}
+        rc = self.L.spg_graph_select_candidates(self.h, int(fixed_id), _p(ij, C.c_int32), _p(rec, C.c_double), n, int(k), float(min_gain),
+                                                float(max_d2), _p(sel, C.c_int32), _p(cg, C.c_double), cap, _p(out["final_gain"], C.c_double),
+                                                _p(out["status"], C.c_int32), C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "selectCandidates")
+        self.last_covariance_stats = st.asdict()
+        out["selected"], out["cond_gain"] = sel[:rc].copy(), cg[:rc].copy()
+        return out
+
     def marginalKullbackLeibler(self, other, fixed_id=-1):
         """Called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other`
         against its marginal here, for every vertex of `other` but the fixed one. Returns (ids, kld), ascending ids.

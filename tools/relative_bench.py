@@ -3,6 +3,12 @@ the current relative pose, Omega = the generator's info_diag), relativeCovarianc
 (the 2D x 2D blocks copied to the host: what a user had to start from before). One JSON line (diagnostic).
 
     python tools/relative_bench.py [--mode score|relative|pairs] [--poses 100000] [--ring 400] [--vertex 50000] [--runs 5]
+    python tools/relative_bench.py --mode select --k K --candidates N [--endpoints 7000]
+
+--mode select: selectCandidates of N random pairs without a common edge, drawn over a random pool of at most --endpoints
+(at most 7 000) vertices, Omega of an existing edge, z = the current relative pose plus noise; select_seconds, rounds and
+endpoints are those of spg_select_stats. The same process also times one scoreCandidates call of the same list
+(score_device_seconds): k of those, plus k addEdge and the round trips, is what the selection replaces.
 
 device_seconds and solve_seconds are those of spg_cov_solve_stats (HIP events: factorisation, column solves, selected
 inverse, assembly and, for score / relative, sp_relative_kernel); wall_seconds is the host clock around the whole call
@@ -23,7 +29,10 @@ from sparsifyposegraph_amd.graph import GraphWrapperHIP  # noqa: E402
 from sparsifyposegraph_amd.lib import Context  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=("score", "relative", "pairs"), default="score")
+ap.add_argument("--mode", choices=("score", "relative", "pairs", "select"), default="score")
+ap.add_argument("--k", type=int, default=10)
+ap.add_argument("--candidates", type=int, default=2000)
+ap.add_argument("--endpoints", type=int, default=7000)
 ap.add_argument("--poses", type=int, default=100000)
 ap.add_argument("--ring", type=int, default=400)
 ap.add_argument("--vertex", type=int, default=50000)
@@ -36,13 +45,32 @@ hg = GraphWrapperHIP.from_dict(g, ctx=ctx)
 ids = hg.vertices()[0]
 v0 = int(ids[min(args.vertex, len(ids) - 1)])
 star = np.array([(v0, int(v)) for v in ids if int(v) != v0], np.int32)
+if args.mode == "select":
+    rng = np.random.default_rng(2024)
+    pool = rng.choice(ids, size=min(args.endpoints, 7000, len(ids)), replace=False)
+    adj = {(min(int(a), int(b)), max(int(a), int(b))) for a, b in g["edge_ij"]}
+    far = []
+    while len(far) < args.candidates:
+        a, b = (int(x) for x in rng.choice(pool, size=2, replace=False))
+        if (min(a, b), max(a, b)) not in adj:
+            far.append((a, b))
+    star = np.array(far, np.int32)
 info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
 meas = None
+if args.mode == "select":
+    meas = hg.relativeCovariances(star)[0]
+    meas[:, :3] += 0.01 * rng.normal(size=(len(star), 3))
+    score_dev = []
+    for _ in range(2):                                  # the second call is the timed one
+        hg.scoreCandidates(star, meas, info)
+        score_dev.append(hg.last_covariance_stats["device_seconds"])
 if args.mode == "score":
     meas = hg.relativeCovariances(star)[0]          # also the warm-up of the factorisation path
 
 
 def call():
+    if args.mode == "select":
+        return sum(v.nbytes for v in hg.selectCandidates(star, meas, info, args.k).values())
     if args.mode == "score":
         return sum(v.nbytes for v in hg.scoreCandidates(star, meas, info).values())
     if args.mode == "relative":
@@ -52,7 +80,7 @@ def call():
 
 
 call()   # warm-up: code objects, allocator
-dev, solve, wall, nbytes, s = [], [], [], 0, None
+dev, solve, wall, nbytes, s, sel = [], [], [], 0, None, []
 for _ in range(args.runs):
     t0 = time.perf_counter()
     nbytes = call()
@@ -60,9 +88,16 @@ for _ in range(args.runs):
     s = hg.last_covariance_stats
     dev.append(s["device_seconds"])
     solve.append(s["solve_seconds"])
+    sel.append(s.get("select_seconds", 0.0))
     print(f"{args.mode}: device {1e3 * dev[-1]:.1f} ms, wall {1e3 * wall[-1]:.1f} ms", file=sys.stderr, flush=True)
+extra = {}
+if args.mode == "select":
+    extra = {"k": args.k, "rounds": s["rounds"], "endpoints": s["endpoints"], "select_seconds": statistics.median(sel),
+             "select_seconds_min": min(sel), "select_seconds_max": max(sel), "score_device_seconds": score_dev[-1],
+             "k_rescorings_device_seconds": args.k * score_dev[-1]}
+what = f"vertex {v0} against all others" if args.mode != "select" else f"{len(star)} random far pairs over a pool of {len(pool)} vertices"
 print(json.dumps({
-    "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: vertex {v0} against all others", "mode": args.mode,
+    "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {what}", "mode": args.mode, **extra,
     "candidates": len(star), "columns": s["columns"], "rhs_batches": s["rhs_batches"], "runs": args.runs,
     "device_seconds": statistics.median(dev), "device_seconds_min": min(dev), "device_seconds_max": max(dev),
     "solve_seconds": statistics.median(solve), "wall_seconds": statistics.median(wall), "wall_seconds_min": min(wall),
