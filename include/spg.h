@@ -499,6 +499,55 @@ int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const int32_t *i
                                 double min_gain, double max_d2, int32_t *selected, double *cond_gain, int cap,
                                 double *final_gain, int32_t *status, spg_select_stats *stats);
 
+/* ---- greedy edge pruning by conditional information loss ---------------------------------------------------
+ * Which k of n of the graph's own binary edges cost the least information when they are removed together: the recurrence
+ * above with the sign turned. A prune candidate is a live binary edge, named by its index in the order of
+ * spg_graph_get_edges; its measurement z_i and information Omega_i = L_i L_i^T are read from the edge's record. With J_i
+ * at z_i, Sigma the covariance of the graph WITH all its edges in the gauge of fixed_id (estimates do not move, the robust
+ * kernel is ignored) and C_ij(0) = J_i Sigma_(ai bi),(aj bj) J_j^T, rounds t = 0, 1, ... run on the device:
+ *   M_i(t)    = I - L_i^T C_ii(t) L_i = G G^T               eigenvalues in [0, 1]; singular exactly when removing the edge
+ *                                                           makes H singular (a bridge, the last constraint of a direction)
+ *   margin_i  = the smallest squared pivot of that Cholesky factorisation
+ *   loss_i(t) = -1/2 ln det M_i(t) >= 0                     = 1/2 (ln det H - ln det(H - A_i^T Omega_i A_i)), nats
+ *   i*        = argmin over the eligible candidates, ties to the lowest index
+ *   B_i,t = C_i*(t) L* G^-T,  C_ii(t+1) = C_ii(t) + B_i,t B_i,t^T,  C_ij(t) = C_ij(0) + sum_{s<t} B_i,s B_j,s^T
+ * which is Sigma' = Sigma + Sigma A^T (Omega^-1 - A Sigma A^T)^-1 A Sigma restricted to candidate space.
+ * Eligible in round t (re-evaluated EVERY round: an edge becomes a bridge when its parallel path is cut): not yet pruned,
+ * Omega finite and positive definite, the factorisation completes and margin >= min_margin (<= 0: the default 1e-6).
+ * Margins only shrink as edges go (C_ii grows in the PSD order), so a candidate that was a bridge in some round never
+ * becomes eligible again. Pruning stops after k rounds, when nothing is eligible, when the best loss is > max_loss
+ * (max_loss <= 0: no limit) or when the cumulative KLD would exceed max_kld (<= 0: no limit).
+ *   kld(t) = sum_{s<=t} loss_s - 1/2 sum_{s<=t} tr(L_s^T C_ss(0) L_s)
+ * is the exact KLD of the pruned graph against the original at the same estimates: what spg_graph_kullback_leibler on the
+ * original with the pruned graph as `other` returns, 1/2 (tr(H_p Sigma) - N + ln det H - ln det H_p), mean term 0.
+ * Memory and SPG_ECAPACITY exactly as spg_graph_select_candidates (joint covariance of the distinct non-fixed endpoints,
+ * min(k, n) D^2 doubles of history per candidate). An endpoint may be the fixed vertex. The graph is NOT modified: apply
+ * the result with spg_graph_remove_edges. An index out of range, a non-binary edge (GLC, MULTI), an index listed twice,
+ * k < 0, an unknown fixed vertex and an active stepwise marginalisation are SPG_EINVAL (the text names the candidate)
+ * before the backend is touched; SPG_ESTATE without HIP. */
+enum { SPG_PRUNE_KEPT = 0, SPG_PRUNE_INFO_NOT_PD = 1, SPG_PRUNE_BRIDGE = 2, SPG_PRUNE_PRUNED = 3 };
+typedef struct {
+    spg_cov_solve_stats solve;   /* the covariance part; its device_seconds covers the pruning too */
+    int32_t rounds;              /* rounds run = edges pruned */
+    int32_t endpoints;           /* m */
+    double prune_seconds;        /* HIP-event time of the pruning alone: initial losses, the rounds, final values */
+} spg_prune_stats;
+/* pruned, cond_loss, kld: min(k, n) entries in order; pruned[t] indexes edge_idx, cond_loss[t] = its loss when it was chosen,
+ * kld[t] = the cumulative KLD after round t; entries beyond the return value are -1 / NaN. Per candidate (n each, each may
+ * be NULL): final_loss = the conditional loss after the last round, NaN unless the status is SPG_PRUNE_KEPT; final_margin =
+ * the margin after the last round, NaN for pruned and not-PD candidates; status = SPG_PRUNE_*, _BRIDGE meaning ineligible by
+ * margin after the last round. Returns the number pruned; with cap < min(k, n) (or pruned / cond_loss / kld NULL) returns
+ * min(k, n) and writes nothing. n = 0 or k = 0 returns 0. */
+int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k,
+                               double max_loss, double max_kld, double min_margin,
+                               int32_t *pruned, double *cond_loss, double *kld, int cap,
+                               double *final_loss, double *final_margin, int32_t *status, spg_prune_stats *stats);
+/* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is
+ * canonicalised first, as spg_graph_get_edges does). Survivors keep their relative order. Bridges may be removed: a
+ * disconnected graph later shows as SPG_ENOTPD. An index out of range or listed twice and an active stepwise
+ * marginalisation are SPG_EINVAL; nothing is changed on error. Host only. */
+int spg_graph_remove_edges(spg_graph *g, const int32_t *edge_idx, int n);
+
 /* ---- optimize() -------------------------------------------------------------
  * GraphWrapperG2O::optimize() (src/graph_wrapper_g2o.cpp:250-269): one vertex fixed (fixed_id < 0: the
  * smallest id), g2o's Levenberg-Marquardt for up to `iterations` iterations (the reference uses 50),

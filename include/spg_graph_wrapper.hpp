@@ -589,6 +589,49 @@ public:
         if (status) status->assign(st.begin(), st.begin() + n);
         return out;
     }
+    // Greedy choice of up to k of the listed live binary edges (indices into the order of spg_graph_get_edges) by
+    // conditional information loss (include/spg.h: spg_graph_prune_candidates); the graph is not modified.
+    struct PruneResult {
+        std::vector<int> pruned;          // indices into edge_idx, in order
+        std::vector<double> cond_loss;    // the loss of pruned[t] when it was chosen
+        std::vector<double> kld;          // the cumulative exact KLD after round t
+        std::vector<double> final_loss, final_margin;   // per candidate, after the last round
+        std::vector<int> status;          // SPG_PRUNE_* per candidate
+    };
+    PruneResult pruneCandidates(const std::vector<int> &edge_idx, int k, double max_loss = 0.0, double max_kld = 0.0, double min_margin = 0.0,
+                                int fixed_id = -1, spg_prune_stats *stats = nullptr) {
+        const int n = (int)edge_idx.size(), cap = std::max(std::min(k, n), 0);
+        std::vector<int32_t> idx(edge_idx.begin(), edge_idx.end()), sel((size_t)std::max(cap, 1)), st((size_t)std::max(n, 1));
+        std::vector<double> loss(sel.size()), kld(sel.size()), fl(st.size()), fm(st.size());
+        const int r = spg_graph_prune_candidates(_g, fixed_id, idx.data(), n, k, max_loss, max_kld, min_margin, sel.data(), loss.data(), kld.data(), cap,
+                                                 fl.data(), fm.data(), st.data(), stats);
+        check(std::min(r, 0), "pruneCandidates");
+        PruneResult out;
+        out.pruned.assign(sel.begin(), sel.begin() + r);
+        out.cond_loss.assign(loss.begin(), loss.begin() + r);
+        out.kld.assign(kld.begin(), kld.begin() + r);
+        out.final_loss.assign(fl.begin(), fl.begin() + n);
+        out.final_margin.assign(fm.begin(), fm.begin() + n);
+        out.status.assign(st.begin(), st.begin() + n);
+        return out;
+    }
+    // live edges: the indices pruneCandidates / removeEdges take run over 0 .. numEdges() - 1 (the order of spg_graph_get_edges)
+    int numEdges() const { return spg_graph_num_edges(_g); }
+    // removes the listed live edges (any kind); the others keep their order (spg_graph_remove_edges)
+    void removeEdges(const std::vector<int> &edge_idx) {
+        std::vector<int32_t> idx(edge_idx.begin(), edge_idx.end());
+        drop_views();
+        check(spg_graph_remove_edges(_g, idx.data(), (int)idx.size()), "removeEdges");
+    }
+    // pruneCandidates followed by removeEdges of what it chose
+    PruneResult pruneEdges(const std::vector<int> &edge_idx, int k, double max_loss = 0.0, double max_kld = 0.0, double min_margin = 0.0,
+                           int fixed_id = -1, spg_prune_stats *stats = nullptr) {
+        PruneResult out = pruneCandidates(edge_idx, k, max_loss, max_kld, min_margin, fixed_id, stats);
+        std::vector<int> gone;
+        for (int t : out.pruned) gone.push_back(edge_idx[(size_t)t]);
+        removeEdges(gone);
+        return out;
+    }
     // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
     // its marginal here, every vertex of `other` but the fixed one; ids ascending
     std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {

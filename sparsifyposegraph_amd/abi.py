@@ -118,6 +118,20 @@ class SelectStats(C.Structure):
         return d
 
 
+# SPG_PRUNE_* (include/spg.h): status of a candidate of spg_graph_prune_candidates
+PRUNE_KEPT, PRUNE_INFO_NOT_PD, PRUNE_BRIDGE, PRUNE_PRUNED = 0, 1, 2, 3
+
+
+class PruneStats(C.Structure):
+    """spg_prune_stats (include/spg.h)"""
+    _fields_ = [("solve", CovSolveStats), ("rounds", C.c_int32), ("endpoints", C.c_int32), ("prune_seconds", C.c_double)]
+
+    def asdict(self):
+        d = self.solve.asdict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_[1:]})
+        return d
+
+
 class OptimizeStats(C.Structure):
     """spg_optimize_stats (include/spg.h)"""
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),

@@ -364,6 +364,19 @@ inline void mark_stale(spg_graph *g, int64_t lo, int64_t hi) {
     else { g->stale_lo = std::min(g->stale_lo, lo); g->stale_hi = std::max(g->stale_hi, hi); }
 }
 
+// A live edge leaves the graph: the live flag, the counters (live_rank is rebuilt on the next use) and the adjacency
+// entries of its vertices. What a committed blanket does to its edges and what spg_graph_remove_edges does.
+inline void retire_edge(spg_graph *g, int32_t eid) {
+    GEdge &e = g->edges[eid];
+    e.alive = 0;
+    g->n_mutations++;
+    g->n_live_e--;
+    for (int i = 0; i < e.nv; i++) {
+        auto &av = g->vr[edge_verts(g, e)[i]].adj;
+        for (size_t j = 0; j < av.size(); j++) if (av[j] == eid) { av[j] = av.back(); av.pop_back(); break; }
+    }
+}
+
 // the HIP backend keeps the text of its last error: make it the context's
 inline void copy_backend_error(spg_ctx *c) { snprintf(c->err, sizeof c->err, "%s", spg::hip_backend_error(&c->be)); }
 

@@ -462,6 +462,27 @@ extern "C" int spg_graph_get_edges(spg_graph *g, int32_t *kind, int32_t *vert_of
     return ne;
 }
 
+extern "C" int spg_graph_remove_edges(spg_graph *g, const int32_t *edge_idx, int n) {
+    const char *what = "spg_graph_remove_edges";
+    if (!g || n < 0 || (n > 0 && !edge_idx)) return SPG_EINVAL;
+    if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    canonicalize_edge_order(g);
+    std::vector<int32_t> live;
+    live.reserve((size_t)g->n_live_e);
+    for (size_t e = 0; e < g->edges.size(); e++) if (g->edges[e].alive) live.push_back((int32_t)e);
+    std::unordered_set<int32_t> seen;
+    for (int i = 0; i < n; i++) {
+        const int32_t x = edge_idx[i];
+        const char *why = (x < 0 || (size_t)x >= live.size()) ? "is out of range" : !seen.insert(x).second ? "is listed twice" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "%s: entry %d: edge %d %s", what, i, (int)x, why);
+            return SPG_EINVAL;
+        }
+    }
+    for (int i = 0; i < n; i++) retire_edge(g, live[edge_idx[i]]);
+    return 0;
+}
+
 extern "C" int spg_graph_set_estimate(spg_graph *g, int id, const double *pose) {
     if (!g || !pose || g->active) return SPG_EINVAL;
     auto it = g->vidx.find(id);

@@ -596,6 +596,72 @@ extern "C" int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const
     return select_call(g, fixed_id, ij, records, n, k, min_gain, max_d2, selected, cond_gain, cap, final_gain, status, stats);
 }
 
+// ================================================================================= greedy edge pruning
+// spg_graph_prune_candidates: candidate i is live edge edge_idx[i] in the order of spg_graph_get_edges, which is the order
+// of the staged edge list; the endpoint set, its joint covariance and the slots are built as in select_call.
+extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k, double max_loss, double max_kld,
+                                          double min_margin, int32_t *pruned, double *cond_loss, double *kld, int cap, double *final_loss,
+                                          double *final_margin, int32_t *status, spg_prune_stats *stats) {
+    const char *what = "spg_graph_prune_candidates";
+    if (!g || n < 0 || (n > 0 && !edge_idx)) return SPG_EINVAL;
+    if (k < 0) return set_err(g->ctx, SPG_EINVAL, "%s: k is negative", what);
+    if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    const int D = g->d;
+    canonicalize_edge_order(g);
+    std::vector<int32_t> live;
+    live.reserve((size_t)g->n_live_e);
+    for (size_t e = 0; e < g->edges.size(); e++) if (g->edges[e].alive) live.push_back((int32_t)e);
+    std::vector<int32_t> S, sa((size_t)n), sb((size_t)n);
+    std::unordered_map<int32_t, int32_t> slot_of;
+    std::unordered_set<int32_t> seen;
+    for (int i = 0; i < n; i++) {
+        const int32_t x = edge_idx[i];
+        const GEdge *ge = (x >= 0 && (size_t)x < live.size()) ? &g->edges[live[x]] : nullptr;
+        const char *why = !ge ? "is out of range" : (ge->kind != SPG_EDGE_BINARY || ge->nv != 2) ? "is not a binary edge"
+                          : ge->vtx[0] == ge->vtx[1] ? "joins a vertex to itself" : !seen.insert(x).second ? "is listed twice" : nullptr;
+        if (why) {
+            snprintf(g->ctx->err, sizeof g->ctx->err, "%s: candidate %d: edge %d %s", what, i, (int)x, why);
+            return SPG_EINVAL;
+        }
+        int32_t sl[2];
+        for (int e = 0; e < 2; e++) {
+            if (ge->vtx[e] == fixed) { sl[e] = -1; continue; }
+            auto it = slot_of.emplace(ge->vtx[e], (int32_t)S.size());
+            if (it.second) S.push_back(ge->vtx[e]);
+            sl[e] = it.first->second;
+        }
+        sa[i] = sl[0]; sb[i] = sl[1];
+    }
+    const int kk = std::min(k, n);
+    if (kk == 0) return 0;
+    const int64_t m = (int64_t)S.size(), W = m * D, need = W * W;
+    if (W > 46000) {
+        snprintf(g->ctx->err, sizeof g->ctx->err, "%s: %lld distinct endpoints, limited to 46k variables, the bound of spg_graph_joint_marginal_covariance",
+                 what, (long long)m);
+        return SPG_ECAPACITY;
+    }
+    if (!pruned || !cond_loss || !kld || cap < kk) return kk;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
+    for (int64_t a = 0; a < m; a++)
+        for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
+    DenseStage st;
+    spg_prune_stats ps{};
+    ps.endpoints = (int32_t)m;
+    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
+    if (staged < 0) return staged;
+    int npruned = 0;
+    if (int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
+                                       edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, min_margin > 0.0 ? min_margin : 1e-6, pruned, cond_loss,
+                                       kld, final_loss, final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (stats) *stats = ps;
+    return npruned;
+}
+
 // ================================================================================= robust kernel
 namespace {
 // The graph's kernel into a staged graph: kind, width and, per live edge in the stage's order, whether it applies — a

@@ -683,17 +683,7 @@ extern "C" int spg_graph_round_commit(spg_graph *g) {
         if (!fine) { g->stats.n_bad_status++; continue; }
         if (!polled && std::isfinite(rec[2])) g->stats.kld_sum += rec[2];
         PT(7);
-        for (int ei_ = 0; ei_ < r.ne; ei_++) {
-            int32_t eid = redges[ei_];
-            GEdge &e = g->edges[eid];
-            e.alive = 0;
-            g->n_mutations++;
-            g->n_live_e--;
-            for (int i = 0; i < e.nv; i++) {
-                auto &av = g->vr[edge_verts(g, e)[i]].adj;
-                for (size_t j = 0; j < av.size(); j++) if (av[j] == eid) { av[j] = av.back(); av.pop_back(); break; }
-            }
-        }
+        for (int ei_ = 0; ei_ < r.ne; ei_++) retire_edge(g, redges[ei_]);
         PT(8);
         for (int i = 0; i < r.n_remove; i++) {
             int32_t v = rverts[i];

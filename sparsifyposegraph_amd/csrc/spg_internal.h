@@ -135,6 +135,13 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
                       int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
                       double min_gain, double max_d2, int32_t *selected, double *cond_gain, double *final_gain, int32_t *status, int *nsel,
                       spg_select_stats &stats, char *err, size_t errlen);
+// Greedy edge pruning (spg_sparse.inc: sp_prune_*_kernel). The sub-block lists and the slots sa / sb as hip_sparse_select;
+// candidate i is live edge eidx[i] of `in` (a binary edge: its record is read from the device arena). n, kk >= 1. pruned,
+// cond_loss, kld: kk entries; final_loss, final_margin, status: n each, may be nullptr.
+int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                     int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
+                     double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
+                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -1054,6 +1054,306 @@ __global__ __launch_bounds__(256) void sp_select_gather_kernel(SelArgs a) {
     if (i < a.n) a.final_gain[i] = a.state[i] == 0 ? a.gain[i] : __builtin_nan("");
 }
 
+// Greedy pruning of the graph's own binary edges by conditional information loss (spg_graph_prune_candidates, DESIGN
+// 5g-P): the recurrence of the selection above with the sign turned. Candidate i is live edge eidx[i] of the staged graph
+// (its record is read from the arena, its endpoints from the staged edge list); with C_ij as above, round t takes i* =
+// argmin of loss_i = -1/2 ln det M_i, M_i = I - L_i^T C_ii L_i = G G^T, over the candidates in state 0 whose smallest
+// squared pivot (the margin) is >= min_margin, and conditions on its removal: B_i,t = C_i*(t) L* G^-T with C_i*(t) =
+// C_i*(0) + sum_{s<t} B_i,s B_*,s^T, C_ii += B_i,t B_i,t^T. States: 0 live, 1 Omega not PD, 3 pruned.
+struct PruneArgs {
+    const double *arena;
+    const int64_t *vpo;
+    const spg_edge_ref *er;   // the staged live edges
+    const int32_t *ev;
+    const int32_t *eidx, *sa, *sb;
+    const double *joint;      // m D x m D, row stride ld
+    long long ld;
+    double *J, *L, *C;        // n x 2 D^2, n x D^2, n x D^2
+    double *hist;             // n x kk x D^2
+    double *loss, *margin;    // n each: of the current round
+    double *tr0;              // n: tr(L_i^T C_ii(0) L_i), the trace term of the KLD
+    int32_t *state;           // n
+    double *pg;               // argmin partials: np losses, np indices
+    int32_t *pi;
+    int32_t *ctl;             // [0] rounds done = number pruned, [1] a stop rule has fired, [2] i* of the current round
+    double *pubC;             // D^2: C_**(t) as it was when i* was picked
+    double *kldsum;           // one double: the cumulative KLD (written by thread 0 of argmin stage 2 alone)
+    int32_t *sel;             // kk: the choices in order
+    double *cl, *ck;          // kk: their conditional losses, the cumulative KLD after each
+    double *final_loss, *final_margin;   // n each
+    int32_t *status;          // n: SPG_PRUNE_*
+    int n, kk, np;
+    double max_loss, max_kld, min_margin;
+};
+// lanes < D^2: M = I - L^T A, r <= c, mirrored
+template <int D>
+__device__ __forceinline__ void rel_M_down(int lane, const double *L, const double *A, double *M) {
+    const int r = lane / D, c = lane - r * D;
+    if (r <= c) {
+        double s = (r == c) ? 1.0 : 0.0;
+        for (int t = r; t < D; t++) s -= L[t * D + r] * A[t * D + c];
+        M[r * D + c] = s;
+        M[c * D + r] = s;
+    }
+}
+// lane 0: M = G G^T in place (lower triangle), checked: stops at the first squared pivot that is not finite, <= 0 or below
+// min_margin (false; loss = NaN). margin = the smallest squared pivot seen (NaN for a pivot that is not finite), loss =
+// -sum log G_jj = -1/2 ln det M.
+template <int D>
+__device__ __forceinline__ bool rel_chol_downdate(double *M, double min_margin, double &loss_out, double &margin_out) {
+    double loss = 0, margin = __builtin_inf();
+    bool ok = true;
+    for (int j = 0; j < D; j++) {
+        double d = M[j * D + j];
+        for (int k = 0; k < j; k++) d -= M[j * D + k] * M[j * D + k];
+        if (!isfinite(d)) { margin = __builtin_nan(""); ok = false; break; }
+        margin = d < margin ? d : margin;
+        if (!(d > 0.0) || d < min_margin) { ok = false; break; }
+        d = sqrt(d);
+        M[j * D + j] = d;
+        loss -= log(d);
+        for (int r = j + 1; r < D; r++) {
+            double v = M[r * D + j];
+            for (int k = 0; k < j; k++) v -= M[r * D + k] * M[j * D + k];
+            M[r * D + j] = v / d;
+        }
+    }
+    loss_out = ok ? loss : __builtin_nan("");
+    margin_out = margin;
+    return ok;
+}
+// One wavefront per candidate, four per workgroup, the LDS slice of sp_select_init_kernel: J, L, C_ii(0) = P, tr0, the
+// loss and the margin of round 0, and the state (Omega not finite or not PD: 1, else 0).
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a) {
+    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3;
+    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n;
+    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
+    double *A = T, *M = T + DD;
+    const spg_edge_ref *er = act ? a.er + a.eidx[i] : nullptr;
+    const double *rec = act ? a.arena + er->off : nullptr;
+    if (act) {
+        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.ev[er->vbegin], a.ev[er->vbegin + 1], rec, nullptr, Ja, Jb, e);
+    }
+    __syncthreads();
+    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
+    __syncthreads();
+    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
+    if (act && lane == 0) {
+        double chi;
+        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
+    }
+    __syncthreads();
+    const bool go = act && okv[w];
+    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
+    __syncthreads();
+    if (go && lane == 0) {           // tr(L^T P L) before M takes A's neighbour
+        double tr = 0;
+        for (int c = 0; c < D; c++)
+            for (int t = c; t < D; t++) tr += L[t * D + c] * A[t * D + c];
+        a.tr0[i] = tr;
+    }
+    if (go && lane < DD) rel_M_down<D>(lane, L, A, M);
+    __syncthreads();
+    if (act && lane == 0) {
+        double loss = __builtin_nan(""), margin = loss;
+        if (go) rel_chol_downdate<D>(M, a.min_margin, loss, margin);
+        else a.tr0[i] = loss;
+        a.loss[i] = loss;
+        a.margin[i] = margin;
+        a.state[i] = go ? 0 : 1;
+    }
+    if (act && lane < DD) {
+        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
+        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
+        a.L[(long long)i * DD + lane] = L[lane];
+        a.C[(long long)i * DD + lane] = P[lane];
+    }
+}
+// (loss ascending, index ascending): the order of the argmin, independent of the grid
+__device__ __forceinline__ bool prn_better(double ga, int ia, double gb, int ib) { return ga < gb || (ga == gb && ia < ib); }
+__device__ __forceinline__ void prn_reduce(double &g, int &i, double *sg, int *si) {
+    const int t = threadIdx.x;
+    sg[t] = g; si[t] = i;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h && prn_better(sg[t + h], si[t + h], sg[t], si[t])) { sg[t] = sg[t + h]; si[t] = si[t + h]; }
+        __syncthreads();
+    }
+    g = sg[0]; i = si[0];
+}
+// Stage 1 (pick == 0, np workgroups): the best (loss, index) per workgroup of the candidates in state 0 that are eligible
+// this round (a loss that is not NaN, margin >= min_margin; the others stay in state 0) into pg / pi. Stage 2 (pick == 1,
+// one workgroup): the best of the partials; none, a loss above max_loss or a cumulative KLD above max_kld: ctl[1] = 1.
+// Else i* is appended to sel / cl / ck, marked pruned, and its C_ii is published for the round kernel.
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a, int pick) {
+    constexpr int DD = D * D;
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    __shared__ int chosen;
+    const int stop = a.ctl[1];   // read by every thread before the first barrier; written after it by thread 0 alone
+    double g = __builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop) {
+        if (!pick) {
+            for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256) {
+                const double l = a.loss[i];
+                if (a.state[i] == 0 && l == l && a.margin[i] >= a.min_margin && prn_better(l, i, g, bi)) { g = l; bi = i; }
+            }
+        } else {
+            for (int p = threadIdx.x; p < a.np; p += 256)
+                if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+        }
+    }
+    prn_reduce(g, bi, sg, si);
+    if (stop) return;
+    if (!pick) {
+        if (threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
+        return;
+    }
+    if (threadIdx.x == 0) {
+        chosen = -1;
+        if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
+            a.ctl[1] = 1;
+        } else {
+            const double kld = a.kldsum[0] + (g - 0.5 * a.tr0[bi]);
+            if (a.max_kld > 0.0 && kld > a.max_kld) {
+                a.ctl[1] = 1;
+            } else {
+                const int c = a.ctl[0];
+                a.sel[c] = bi;
+                a.cl[c] = g;
+                a.ck[c] = kld;
+                a.kldsum[0] = kld;
+                a.ctl[0] = c + 1;
+                a.ctl[2] = bi;
+                a.state[bi] = 3;
+                chosen = bi;
+            }
+        }
+    }
+    __syncthreads();
+    if (chosen >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)chosen * DD + threadIdx.x];
+}
+// Conditions every candidate still in state 0, and i* itself, on the removal of i* (read from ctl), then re-evaluates the
+// candidate's own M, loss and margin. One wavefront per candidate. M of i* passed the margin test when it was picked; if
+// its factorisation fails all the same, the candidate gets a NaN loss and margin and nothing else of it is touched.
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a) {
+    constexpr int W = 2 * D, DD = D * D;
+    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
+    const int s = a.ctl[2], t = a.ctl[0] - 1;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
+    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
+           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD;
+    if (act) {
+        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
+        for (int k = lane; k < 2 * DD; k += 64) {
+            Ji[k] = a.J[(long long)i * 2 * DD + k];
+            Js[k] = a.J[(long long)s * 2 * DD + k];
+        }
+        if (lane < DD) {
+            Ls[lane] = a.L[(long long)s * DD + lane];
+            Ms[lane] = a.pubC[lane];
+            Li[lane] = a.L[(long long)i * DD + lane];
+            Ci[lane] = a.C[(long long)i * DD + lane];
+        }
+    }
+    __syncthreads();
+    if (act) {
+        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
+        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        rel_M_down<D>(lane, Ls, As, Ms);               // M = I - L*^T C** L*
+        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
+        double x = 0;
+        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
+        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
+        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
+        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
+            x += d;
+        }
+        X[lane] = x;
+    }
+    __syncthreads();
+    if (act && lane == 0) {
+        double l, m;
+        okv[w] = rel_chol_downdate<D>(Ms, 0.0, l, m);  // G in the lower triangle of Ms
+        if (!okv[w]) { a.loss[i] = __builtin_nan(""); a.margin[i] = __builtin_nan(""); }
+    }
+    __syncthreads();
+    const bool upd = act && okv[w];
+    if (upd && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
+        const int r = lane;
+        for (int j = 0; j < D; j++) {
+            double v = (j <= r) ? Ls[r * D + j] : 0.0;
+            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
+            K[r * D + j] = v / Ms[j * D + j];
+        }
+    }
+    __syncthreads();
+    if (upd && lane < DD) {                            // B_i,t = X K, appended to the history
+        const int r = lane / D, c = lane - r * D;
+        double v = 0;
+        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
+        B[lane] = v;
+        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
+    }
+    __syncthreads();
+    if (upd && lane < DD) {                            // C_ii += B B^T, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
+            const double v = Ci[r * D + c] + d;
+            Ci[r * D + c] = v;
+            Ci[c * D + r] = v;
+        }
+    }
+    __syncthreads();
+    const bool re = upd && go;
+    if (upd && lane < DD) {
+        a.C[(long long)i * DD + lane] = Ci[lane];
+        if (go) rel_PL<D>(lane, Ci, Li, As);
+    }
+    __syncthreads();
+    if (re && lane < DD) rel_M_down<D>(lane, Li, As, Ms);
+    __syncthreads();
+    if (re && lane == 0) {
+        double l, m;
+        rel_chol_downdate<D>(Ms, a.min_margin, l, m);
+        a.loss[i] = l;
+        a.margin[i] = m;
+    }
+}
+// final_loss / final_margin / status after the last round: a candidate still in state 0 is SPG_PRUNE_BRIDGE when its
+// margin is below min_margin or NaN (final_loss NaN), else SPG_PRUNE_KEPT
+__global__ __launch_bounds__(256) void sp_prune_gather_kernel(PruneArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const double nan = __builtin_nan("");
+    const int st = a.state[i];
+    const double l = a.loss[i], m = a.margin[i];
+    const bool kept = st == 0 && l == l && m >= a.min_margin;
+    a.final_loss[i] = kept ? l : nan;
+    a.final_margin[i] = st == 0 ? m : nan;
+    a.status[i] = st != 0 ? st : kept ? 0 : 2;
+}
+
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
 // (src/utils.cpp:70-97) = 0.5 (tr(Sx^-1 Sy) + diff^T Sx^-1 diff + log det Sx - log det Sy - D), through the Cholesky
 // factors Sx = Lx Lx^T, Sy = Ly Ly^T: tr = || Lx^-1 Ly ||_F^2, Mahalanobis = || Lx^-1 diff ||^2. One lane per vertex,
@@ -2306,6 +2606,102 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     *nsel = ctl[0];
     stats.rounds = ctl[0];
     stats.select_seconds = 1e-3 * ms;
+    return 0;
+}
+
+// spg_graph_prune_candidates: the sub-block lists and slots as hip_sparse_select; candidate i is live edge eidx[i] of the
+// staged graph. The tail enqueues init, kk x (argmin, argmin, round) and the gather without a synchronisation. pruned /
+// cond_loss / kld: kk entries (the tail beyond *npruned is -1 / NaN), final_loss / final_margin / status: n each, may be
+// nullptr. Host arrays throughout.
+int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                     int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
+                     double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
+                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen) {
+    hipStream_t s = (hipStream_t)stream;
+    const int D = in.D, DD = D * D;
+    const int np = std::min((n + 255) / 256, 256);
+    int rc = 0;
+    {
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
+        if (bytes + (double)(1ull << 30) > (double)free_b) {
+            snprintf(err, errlen, "edge pruning needs %.1f GB for the joint covariance of the endpoints and the histories, %.1f GB are free",
+                     bytes * 1e-9, free_b * 1e-9);
+            return SPG_ECAPACITY;
+        }
+    }
+    DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus;
+    if ((rc = upload(deidx, eidx, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) || (rc = upload(dsb, sb, (size_t)n, s))) {
+        snprintf(err, errlen, "staging the candidates failed (%d)", rc);
+        return rc;
+    }
+    HIPCHK(hipMalloc(&dJ.p, (size_t)n * 2 * DD * 8));
+    HIPCHK(hipMalloc(&dL.p, (size_t)n * DD * 8));
+    HIPCHK(hipMalloc(&dC.p, (size_t)n * DD * 8));
+    HIPCHK(hipMalloc(&dhist.p, (size_t)n * kk * DD * 8));
+    HIPCHK(hipMalloc(&dloss.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dmargin.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dtr0.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dstate.p, (size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dpg.p, (size_t)np * 8));
+    HIPCHK(hipMalloc(&dpi.p, (size_t)np * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dctl.p, 4 * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dpub.p, (size_t)DD * 8));
+    HIPCHK(hipMalloc(&dksum.p, 8));
+    HIPCHK(hipMalloc(&dsel.p, (size_t)kk * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dcl.p, (size_t)kk * 8));
+    HIPCHK(hipMalloc(&dck.p, (size_t)kk * 8));
+    HIPCHK(hipMalloc(&dfl.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dfm.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&dstatus.p, (size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMemsetAsync(dctl.p, 0, 4 * sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(dksum.p, 0, 8, s));
+    HIPCHK(hipMemsetAsync(dsel.p, 0xff, (size_t)kk * sizeof(int32_t), s));   // -1
+    HIPCHK(hipMemsetAsync(dcl.p, 0xff, (size_t)kk * 8, s));                  // NaN
+    HIPCHK(hipMemsetAsync(dck.p, 0xff, (size_t)kk * 8, s));
+    EventTimer t_prune;
+    hipError_t tail_err = hipSuccess;
+    const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
+        PruneArgs a{};
+        a.arena = gb.dev.arena; a.vpo = gb.dev.vpo; a.er = gb.dev.er; a.ev = gb.dev.ev;
+        a.eidx = (const int32_t *)deidx.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
+        a.joint = joint; a.ld = ld;
+        a.J = (double *)dJ.p; a.L = (double *)dL.p; a.C = (double *)dC.p; a.hist = (double *)dhist.p;
+        a.loss = (double *)dloss.p; a.margin = (double *)dmargin.p; a.tr0 = (double *)dtr0.p; a.state = (int32_t *)dstate.p;
+        a.pg = (double *)dpg.p; a.pi = (int32_t *)dpi.p; a.ctl = (int32_t *)dctl.p; a.pubC = (double *)dpub.p; a.kldsum = (double *)dksum.p;
+        a.sel = (int32_t *)dsel.p; a.cl = (double *)dcl.p; a.ck = (double *)dck.p;
+        a.final_loss = (double *)dfl.p; a.final_margin = (double *)dfm.p; a.status = (int32_t *)dstatus.p;
+        a.n = n; a.kk = kk; a.np = np; a.max_loss = max_loss; a.max_kld = max_kld; a.min_margin = min_margin;
+        const dim3 per_cand((unsigned)((n + 3) / 4));
+        tail_err = t_prune.start(st);
+        by_dim(D, [&](auto d) {
+            constexpr int DV = decltype(d)::value;
+            hipLaunchKernelGGL((sp_prune_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
+            for (int t = 0; t < kk; t++) {
+                hipLaunchKernelGGL((sp_prune_argmin_kernel<DV>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
+                hipLaunchKernelGGL((sp_prune_argmin_kernel<DV>), dim3(1), dim3(256), 0, st, a, 1);
+                hipLaunchKernelGGL((sp_prune_round_kernel<DV>), per_cand, dim3(256), 0, st, a);
+            }
+        });
+        hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        if (tail_err == hipSuccess) tail_err = t_prune.stop(st);
+    };
+    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail))) return rc;
+    HIPCHK(tail_err);
+    float ms = 0;
+    HIPCHK(t_prune.ms(ms));
+    int32_t ctl[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(ctl, dctl.p, sizeof ctl, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pruned, dsel.p, (size_t)kk * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cond_loss, dcl.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(kld, dck.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
+    if (final_loss) HIPCHK(hipMemcpy(final_loss, dfl.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (final_margin) HIPCHK(hipMemcpy(final_margin, dfm.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dstatus.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *npruned = ctl[0];
+    stats.rounds = ctl[0];
+    stats.prune_seconds = 1e-3 * ms;
     return 0;
 }
 

@@ -468,6 +468,42 @@ class GraphWrapperHIP:
         out["selected"], out["cond_gain"] = sel[:rc].copy(), cg[:rc].copy()
         return out
 
+    def pruneCandidates(self, edge_idx, k, max_loss=0.0, max_kld=0.0, min_margin=0.0, fixed_id=-1):
+        """Greedy choice of up to k of the listed live binary edges (indices into the order of edges()) by conditional
+        information loss (include/spg.h: spg_graph_prune_candidates): each round takes the edge whose removal costs the
+        least given the ones already taken (ties: the lowest index), on the device, without modifying the graph. An edge
+        whose removal would make the information singular to min_margin (<= 0: 1e-6) is not eligible; that is re-evaluated
+        every round. Stops early on max_loss / max_kld (<= 0: no limit). Returns a dict: pruned int32[r] (indices into
+        edge_idx, in order), cond_loss float64[r], kld float64[r] (cumulative, exact at the stored estimates), final_loss,
+        final_margin float64[n], status int32[n] (abi.PRUNE_*). Stats (abi.PruneStats) in `last_covariance_stats`."""
+        st = abi.PruneStats()
+        idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
+        n = len(idx)
+        cap = max(min(int(k), n), 0)
+        sel, cl, ck = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), np.nan), np.full(max(cap, 1), np.nan)
+        out = {"final_loss": np.full(n, np.nan), "final_margin": np.full(n, np.nan), "status": np.zeros(n, np.int32)}
+        rc = self.L.spg_graph_prune_candidates(self.h, int(fixed_id), _p(idx, C.c_int32), n, int(k), float(max_loss), float(max_kld),
+                                               float(min_margin), _p(sel, C.c_int32), _p(cl, C.c_double), _p(ck, C.c_double), cap,
+                                               _p(out["final_loss"], C.c_double), _p(out["final_margin"], C.c_double),
+                                               _p(out["status"], C.c_int32), C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "pruneCandidates")
+        self.last_covariance_stats = st.asdict()
+        out["pruned"], out["cond_loss"], out["kld"] = sel[:rc].copy(), cl[:rc].copy(), ck[:rc].copy()
+        return out
+
+    def removeEdges(self, edge_idx):
+        """Removes the listed live edges (indices into the order of edges(), any kind); the others keep their order
+        (include/spg.h: spg_graph_remove_edges)."""
+        idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
+        check(self.L.spg_graph_remove_edges(self.h, _p(idx, C.c_int32), len(idx)), self.ctx.h, "removeEdges")
+
+    def pruneEdges(self, edge_idx, k, max_loss=0.0, max_kld=0.0, min_margin=0.0, fixed_id=-1):
+        """pruneCandidates followed by removeEdges of what it chose; returns pruneCandidates' dict."""
+        idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
+        out = self.pruneCandidates(idx, k, max_loss, max_kld, min_margin, fixed_id)
+        self.removeEdges(idx[out["pruned"]])
+        return out
+
     def marginalKullbackLeibler(self, other, fixed_id=-1):
         """Called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other`
         against its marginal here, for every vertex of `other` but the fixed one. Returns (ids, kld), ascending ids.

@@ -1,0 +1,732 @@
+"""Greedy edge pruning by conditional information loss and its exact KLD (spg_graph_prune_candidates /
+spg_graph_remove_edges, csrc/spg_sparse.inc: sp_prune_init_kernel / _argmin_kernel / _round_kernel) against the numpy rule
+of tests/prune_ref.py.
+CPU: the candidate-space recurrence equals the rule on the dense information (slogdet) and the Woodbury form, the KLD
+closed form, dynamic eligibility on a 4-cycle, the GPU lists are decidable, the argument contract and removeEdges on an
+injected backend, the ABI and the bindings, the C++ demo compiles.
+GPU: sequence and values on constructed lists (before and after marginalisation, both gauges), round-0 losses and margins
+of every binary edge of a graph and its bridges, the KLD and log det identities through pruneEdges, the inverse relation
+with selectCandidates, the stop rules and sizes, untouched behaviour, the C++ façade.
+
+Bounds (derived, not measured). single_i = 1/2 D ||Omega_i||2 D beta_i with beta_i = ||J_i||inf^2 1e-9 max|Sigma| + 1e-11
+max|C_ii(0)| is the bound of a single gain in tests/test_candidate_selection.py: D ||Omega|| beta bounds ||dM|| for
+M = I -+ L^T C L. There M >= I; here M = I - L^T C L has eigenvalues in (0, 1], and d(ln det M) = tr(M^-1 dM) <= D ||dM|| /
+lambda_min(M): a loss read in round t is amplified by 1 / lambda_min(M_i(t)). Each earlier conditioning s added
+B B^T = C_i* K K^T C_*i with K K^T = L* M*^-1 L*^T, a term of the form of C_ii times at most 1 / lambda_min(M*_s) (in the
+selection M* >= I kept it below the first), so
+    bound_i(t) = (t + 1) single_i / (lambda_min(M_i(t)) min(1, min_{s<t} lambda_min(M*_s)))
+with the reference's eigenvalues. kld(t) adds the trace terms 1/2 tr(L_s^T C_ss(0) L_s), each within D/2 ||dM|| = single_s:
+kld_bound(t) = sum_{s<=t} (bound_s(s) + single_s). A margin (the smallest squared pivot, a Schur complement 1 / (M_j^-1)_jj
+of a leading block, <= 1) moves by at most ||dM|| / lambda_min(M)^2 = (2 single_i / D) / lambda_min(M_i)^2.
+The lists are decidable when in every round the best candidate leads the second best by 10 times the larger of their two
+bounds; at the scale of a graph's own edges that does not hold (exact ties on the manhattan lattice), so no test asserts a
+sequence over a fixture's own edges. The sequence lists are 40 added edges between far pairs at the current relative pose
+with isotropic informations graded weakest-first (GRADE).
+Measured on an MI355X, worst error over its bound (cond_loss, kld, final_loss, final_margin): 9.2e-6 (intel), 2.7e-7
+(sphere), 1.25e-4 (manhattan GLC Tree), 2.3e-7 (synth_manhattan, 300 candidates); the sum of the losses against 1/2 delta
+ln det of information(): 8.8e-4, 3.3e-6 and 1.8e-3 of what is allowed; kld against kullbackLeibler: 1.9e-5, 1.9e-7, 2.5e-6.
+Smallest lead over 10 bounds (numpy alone): intel 234, sphere 3.76, manhattan GLC Tree 35.8, synth_manhattan 653. Device
+margins: bridges at most 3.0e-12 in absolute value, non-bridges at least 1.03e-3 (intel after NFR Tree).
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from sparsifyposegraph_amd import abi, g2o_io, lib
+from sparsifyposegraph_amd.lib import SpgError
+from tests import oracle_lib, util
+from tests import prune_ref as pr
+from tests import relative_ref as rr
+from tests import select_ref as sr
+from tests.test_candidate_selection import _at, _oracle_graphs, _poses, _random_problem, _single_bounds, _fids
+from tests.test_covariance_blocks import _oracle_of, _small
+from tests.test_relative_covariance import _far_pairs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "sparsifyposegraph_amd")
+_f64p, _i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+EINVAL, ESTATE = -1, -7
+CASES = [("intel_nfr_tree_sp3", 600), ("sphere_nfr_tree", 500), ("manhattan_glc_tree", 600)]
+GRADE = (0.5, 2.0, 20)      # base, g, cap: s_i = base g^-(cap - min(rank_i, cap)) / lambda_i
+K, N_ADD = 8, 40
+
+
+# ------------------------------------------------------------------------------------------------- shared helpers
+def _graded_edges(d, view, fid, Sig):
+    """The constructed list on a graph view with covariance Sig (both BEFORE the additions): 40 far pairs, z = the current
+    relative pose, Omega = s_i I with s_i = base g^-(cap - min(c_i, cap)) / lambda_i, lambda_i = tr(C_ii) / D and c_i the
+    rank by descending q_i = lambda_i / (||J_i||inf^2 max|Sigma|): the tightest bound gives the weakest edge, which is
+    pruned first. Returns (ij, meas, info_upper, rank)."""
+    base, g, cap = GRADE
+    ids = [int(i) for i in view.vertices()[0]]
+    poses = _poses(view)
+    far = _far_pairs(view, N_ADD, seed=fid)
+    meas = np.array([rr.between(d, poses[int(a)], poses[int(b)]) for a, b in far])
+    unit = np.tile(rr.upper(np.eye(d)), (N_ADD, 1))
+    T = sr.terms(d, poses, _at(ids, fid), far, meas, unit)
+    scale = float(np.abs(Sig).max())
+    lam, q = np.zeros(N_ADD), np.zeros(N_ADD)
+    for i, t in enumerate(T):
+        idx, J = sr._support(t, d)
+        lam[i] = np.trace(J @ Sig[np.ix_(idx, idx)] @ J.T) / d
+        q[i] = lam[i] / (np.abs(t["J"]).sum(axis=1).max() ** 2 * scale)
+    rank = np.zeros(N_ADD, int)
+    rank[np.argsort(-q, kind="stable")] = np.arange(N_ADD)
+    info = np.array([rr.upper(base * g ** -(cap - min(int(rank[i]), cap)) / lam[i] * np.eye(d)) for i in range(N_ADD)])
+    return far, meas, info, rank
+
+
+def _problem(d, view, fid, H0):
+    """The constructed list, the information H1 with the 40 edges added, its inverse and the candidates' terms"""
+    ids = [int(i) for i in view.vertices()[0]]
+    ij, meas, info, rank = _graded_edges(d, view, fid, np.linalg.inv(H0))
+    T = sr.terms(d, _poses(view), _at(ids, fid), ij, meas, info)
+    H1 = H0 + sum(t["A"].T @ t["Om"] @ t["A"] for t in T)
+    return ij, meas, info, rank, T, H1, np.linalg.inv(H1)
+
+
+def _bounds(ref, single):
+    """bound_i(t) of the module docstring for every round of a reference run (and the round after the last): a list of
+    {i: bound}, and the cumulative KLD bound per round"""
+    out, kb, worst_star, acc = [], [], 1.0, 0.0
+    for t, ev in enumerate(ref["rounds"]):
+        out.append({i: (t + 1) * single[i] / (max(v[2], 1e-300) * worst_star) for i, v in ev.items()})
+        if t < len(ref["pruned"]):
+            s = int(ref["pruned"][t])
+            acc += out[t][s] + single[s]
+            kb.append(acc)
+            worst_star = min(worst_star, ev[s][2])
+    return out, np.array(kb), worst_star
+
+
+def _lead(ref, bounds):
+    """smallest (second best - best) / (10 * larger bound) over the rounds of a reference run"""
+    worst = np.inf
+    for t in range(len(ref["pruned"])):
+        ev, best = ref["rounds"][t], int(ref["pruned"][t])
+        others = [i for i in ev if i != best and not np.isnan(ev[i][0])]
+        if not others:
+            continue
+        second = min(others, key=lambda i: ev[i][0])
+        worst = min(worst, (ev[second][0] - ev[best][0]) / (10.0 * max(bounds[t][best], bounds[t][second])))
+    return worst
+
+
+def _manhattan_list(view, fid, H0, n=300):
+    """300 far-pair edges on synth_manhattan(400) at the current relative pose, isotropic informations 0.5 2^-max(12 - i, 0) /
+    lambda_i (the first twelve graded weakest-first, the rest equal), candidate 5 an edge to the fixed vertex, candidate 7
+    a small indefinite Omega. Returns (ij, meas, info, T, usable, H1 = H0 with all of them added)."""
+    d = 3
+    ids = [int(i) for i in view.vertices()[0]]
+    Sig0 = np.linalg.inv(H0)
+    poses = _poses(view)
+    far = _far_pairs(view, n, seed=78)
+    far[5] = (fid, ids[len(ids) // 2])
+    meas = np.array([rr.between(d, poses[int(a)], poses[int(b)]) for a, b in far])
+    T0 = sr.terms(d, poses, _at(ids, fid), far, meas, np.tile(rr.upper(np.eye(d)), (n, 1)))
+    lam = np.zeros(n)
+    for i, t in enumerate(T0):
+        idx, J = sr._support(t, d)
+        lam[i] = np.trace(J @ Sig0[np.ix_(idx, idx)] @ J.T) / d
+    info = np.array([rr.upper(0.5 * 2.0 ** -max(12 - i, 0) / lam[i] * np.eye(d)) for i in range(n)])
+    info[7] = rr.upper(0.01 / lam[7] * np.diag([1.0, -1.0, 1.0]))
+    T = sr.terms(d, poses, _at(ids, fid), far, meas, info)
+    ok = [t["ok"] for t in T]
+    assert not ok[7] and sum(ok) == n - 1
+    H1 = H0 + sum(t["A"].T @ t["Om"] @ t["A"] for t in T)      # the indefinite record is in the graph too
+    return far, meas, info, T, ok, H1
+
+
+# ------------------------------------------------------------------------------------------------------- CPU
+def _legal_problem(d, seed, n_cand=12):
+    """H = H0 + sum A^T Omega A over the candidates of select's random problem: every removal is legal"""
+    H0, T = _random_problem(d, seed, n_cand)
+    return H0, T, H0 + sum(t["A"].T @ t["Om"] @ t["A"] for t in T)
+
+
+@pytest.mark.parametrize("d", [3, 6])
+def test_recurrence_equals_the_rule_on_the_dense_information(d):
+    """Random SPD H0 over 8 poses plus 12 candidate edges, k = 6: the recurrence and the Woodbury form give the sequence of
+    the slogdet rule, its losses and the KLD to 1e-10 (relative); the losses sum to 1/2 delta ln det; the KLD equals the
+    trace / log det formula; the conditional loss of a fixed candidate never decreases; the stop rules."""
+    H0, T, H = _legal_problem(d, seed=d)
+    ok = [True] * len(T)
+    exact = pr.greedy(H, T, ok, 6)
+    Sig = np.linalg.inv(H)
+    assert len(exact["pruned"]) == 6
+    for other in (pr.recurrence(Sig, T, ok, 6), pr.greedy_sigma(Sig, T, ok, 6)):
+        assert np.array_equal(other["pruned"], exact["pruned"])
+        assert np.allclose(other["cond_loss"], exact["cond_loss"], rtol=1e-10, atol=0)
+        assert np.allclose(other["kld"], exact["kld"], rtol=1e-10, atol=0)
+        live = ~np.isnan(exact["final_loss"])
+        assert np.array_equal(live, ~np.isnan(other["final_loss"])) and live.sum() == 6
+        assert np.allclose(other["final_loss"][live], exact["final_loss"][live], rtol=1e-10, atol=0)
+        assert np.allclose(other["final_margin"][live], exact["final_margin"][live], rtol=1e-9, atol=0)
+        assert np.array_equal(other["status"], exact["status"])
+        for t in range(1, len(other["rounds"])):
+            for i, v in other["rounds"][t].items():
+                assert v[0] >= other["rounds"][t - 1][i][0] * (1 - 1e-12) and v[1] <= other["rounds"][t - 1][i][1] * (1 + 1e-12)
+    want = 0.5 * (np.linalg.slogdet(H)[1] - np.linalg.slogdet(exact["H"])[1])
+    assert exact["cond_loss"].sum() == pytest.approx(want, rel=1e-12) and np.all(exact["cond_loss"] > 0)
+    Hp = H.copy()
+    for t, s in enumerate(exact["pruned"]):
+        Hp = Hp - T[s]["A"].T @ T[s]["Om"] @ T[s]["A"]
+        assert exact["kld"][t] == pytest.approx(pr.kld_trace_logdet(H, Hp), rel=1e-9)
+    assert np.all(np.diff(exact["kld"]) > 0)
+    # max_loss between the third and the fourth loss stops after three; max_kld between two cumulative values at the earlier
+    mid = 0.5 * (exact["cond_loss"][2] + exact["cond_loss"][3])
+    assert np.array_equal(pr.recurrence(Sig, T, ok, 6, max_loss=mid)["pruned"], exact["pruned"][:3])
+    midk = 0.5 * (exact["kld"][3] + exact["kld"][4])
+    assert np.array_equal(pr.recurrence(Sig, T, ok, 6, max_kld=midk)["pruned"], exact["pruned"][:4])
+
+
+@pytest.mark.parametrize("d", [3, 6])
+def test_second_of_two_identical_edges(d):
+    """Two identical copies of one edge: removing the first raises the second's loss to the closed form with
+    P <- (P^-1 - Omega)^-1, the covariance of its error once the first copy is gone."""
+    H0, T = _random_problem(d, seed=10 + d, n_cand=3)
+    T = [T[1], T[1]]
+    H = H0 + 2 * T[0]["A"].T @ T[0]["Om"] @ T[0]["A"]
+    Sig = np.linalg.inv(H)
+    got = pr.recurrence(Sig, T, [True, True], 2)
+    assert got["pruned"].tolist() == [0, 1]
+    idx, J = sr._support(T[0], d)
+    P, Om = J @ Sig[np.ix_(idx, idx)] @ J.T, T[0]["Om"]
+    assert got["cond_loss"][0] == pytest.approx(-0.5 * np.linalg.slogdet(np.eye(d) - Om @ P)[1], rel=1e-10)
+    P1 = np.linalg.inv(np.linalg.inv(P) - Om)
+    assert got["cond_loss"][1] == pytest.approx(-0.5 * np.linalg.slogdet(np.eye(d) - Om @ P1)[1], rel=1e-9)
+    assert got["cond_loss"][1] > got["cond_loss"][0]
+
+
+def _cycle_graph():
+    """Four SE2 poses on a unit square, the four edges of the cycle at the exact relative poses, unit information"""
+    poses = np.array([[0, 0, 0], [1, 0, np.pi / 2], [1, 1, np.pi], [0, 1, -np.pi / 2]], np.float64)
+    ij = np.array([(0, 1), (1, 2), (2, 3), (3, 0)], np.int32)
+    meas = np.array([rr.between(3, poses[a], poses[b]) for a, b in ij])
+    data = np.concatenate([meas, np.tile(rr.upper(np.eye(3)), (4, 1))], axis=1)
+    return {"pose_dim": 3, "ids": np.arange(4, dtype=np.int32), "poses": poses, "edge_ij": ij, "edge_data": data}
+
+
+def _cycle_reference(g):
+    poses = {int(i): p for i, p in zip(g["ids"], g["poses"])}
+    T = sr.terms(3, poses, {1: 0, 2: 1, 3: 2}, g["edge_ij"], g["edge_data"][:, :3], g["edge_data"][:, 3:])
+    H = sum(t["A"].T @ t["Om"] @ t["A"] for t in T)
+    return T, H
+
+
+def test_eligibility_is_dynamic_on_a_cycle():
+    """On a 4-cycle any one edge is prunable; after one is pruned the remaining three are bridges: k = 4 returns 1 and
+    three BRIDGE statuses, in all three reference forms; connectivity agrees."""
+    g = _cycle_graph()
+    T, H = _cycle_reference(g)
+    assert pr.connectivity_bridges(4, g["edge_ij"].tolist()) == [] and pr.connectivity_bridges(4, g["edge_ij"][1:].tolist()) == [0, 1, 2]
+    for cyc in (g, _tie_free_cycle()):
+        T, H = _cycle_reference(cyc)
+        runs = [pr.greedy(H, T, [True] * 4, 4), pr.greedy_sigma(np.linalg.inv(H), T, [True] * 4, 4), pr.recurrence(np.linalg.inv(H), T, [True] * 4, 4)]
+        for ref in runs:
+            assert len(ref["pruned"]) == 1       # (on the symmetric cycle the four losses differ by rounding only: any of them)
+            rest = np.arange(4) != ref["pruned"][0]
+            assert np.all(ref["status"][rest] == pr.BRIDGE) and ref["status"][~rest].tolist() == [pr.PRUNED]
+            assert np.all(np.isnan(ref["final_loss"])) and np.all(np.abs(ref["final_margin"][rest]) < 1e-9)
+            assert all(v[1] > 1e-3 for v in ref["rounds"][0].values())      # far above min_margin: all four are prunable
+        if cyc is not g:
+            assert runs[0]["pruned"].tolist() == runs[1]["pruned"].tolist() == runs[2]["pruned"].tolist()
+
+
+def _tie_free_cycle():
+    """the 4-cycle with graded informations, so that the first choice does not rest on a tie"""
+    g = _cycle_graph()
+    for e, s in enumerate((2.0, 1.0, 3.0, 4.0)):
+        g["edge_data"][e, 3:] = rr.upper(s * np.eye(3))
+    return g
+
+
+@pytest.mark.parametrize("case,n", CASES)
+def test_constructed_lists_are_decidable(case, n):
+    """A condition on the inputs of the GPU sequence test: on the oracle's graphs (before and after its own marginalisation,
+    both gauges) the rule prunes eight of the weakest-graded edges of the constructed list (rank order up to the effect the
+    other additions have on the covariance) and every round's lead is at least 10 bounds; the slogdet rule agrees with the Woodbury form on the first three rounds of one configuration."""
+    sub, graphs, kept = _oracle_graphs(case, n)
+    d = sub["pose_dim"]
+    worst, checked_exact = np.inf, False
+    for og in graphs:
+        ids = [int(i) for i in og.vertices()[0]]
+        for fid in _fids(ids, kept):
+            H0 = og.information(fid)
+            ij, meas, info, rank, T, H1, Sig1 = _problem(d, og, fid, H0)
+            ref = pr.greedy_sigma(Sig1, T, [True] * N_ADD, K)
+            single = _single_bounds(d, T, Sig1)
+            bounds, kb, _ = _bounds(ref, single)
+            lead = _lead(ref, bounds)
+            worst = min(worst, lead)
+            print(f"{case}[{n}] fixed {fid}: ranks pruned {rank[ref['pruned']].tolist()}, lead / (10 bounds) {lead:.2e}")
+            assert len(ref["pruned"]) == K and rank[ref["pruned"]].max() < 2 * K and lead >= 1.0, (case, fid, rank[ref["pruned"]], lead)
+            if og is graphs[1] and not checked_exact:
+                exact = pr.greedy(H1, T, [True] * N_ADD, 3)
+                atol = 1e-12 * abs(np.linalg.slogdet(H1)[1])
+                assert np.array_equal(exact["pruned"], ref["pruned"][:3])
+                assert np.allclose(exact["cond_loss"], ref["cond_loss"][:3], rtol=1e-9, atol=atol)
+                assert np.allclose(exact["kld"], ref["kld"][:3], rtol=1e-9, atol=3 * atol)
+                assert exact["kld"][-1] == pytest.approx(pr.kld_trace_logdet(H1, exact["H"]), rel=1e-6, abs=3 * atol)
+                checked_exact = True
+    print(f"{case}[{n}]: smallest lead / (10 bounds) {worst:.2e}")
+    assert checked_exact
+
+
+def test_manhattan_list_is_decidable():
+    g = g2o_io.synth_manhattan(n_poses=400, side=20)
+    og = oracle_lib.OracleGraph.from_dict(g)
+    fid = int(g["ids"][0])
+    ij, meas, info, T, ok, H1 = _manhattan_list(og, fid, og.information(fid))
+    Sig1 = np.linalg.inv(H1)
+    single = _single_bounds(3, T, Sig1)
+    single[7] = np.inf
+    ref = pr.greedy_sigma(Sig1, T, ok, 5)
+    bounds, kb, _ = _bounds(ref, single)
+    lead = _lead(ref, bounds)
+    print(f"synth_manhattan(400), 300 candidates: smallest lead / (10 bounds) {lead:.2e}")
+    assert ref["pruned"].tolist() == [0, 1, 2, 3, 4] and lead >= 1.0
+    # the stop rules of the GPU test: the midpoints are 10 bounds from both neighbours
+    mid = 0.5 * (ref["cond_loss"][2] + ref["cond_loss"][3])
+    assert min(mid - ref["cond_loss"][2], ref["cond_loss"][3] - mid) >= 10 * max(bounds[2][2], bounds[3][3])
+    midk = 0.5 * (ref["kld"][1] + ref["kld"][2])
+    assert min(midk - ref["kld"][1], ref["kld"][2] - midk) >= 10 * kb[2]
+
+
+def test_abi_and_bindings_cover_the_pruning():
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    L = C.CDLL(lib.LIB_PATH)
+    for name in ("spg_graph_prune_candidates", "spg_graph_remove_edges"):
+        assert name in lib.SYMBOLS and hasattr(L, name)
+    assert (abi.PRUNE_KEPT, abi.PRUNE_INFO_NOT_PD, abi.PRUNE_BRIDGE, abi.PRUNE_PRUNED) == (0, 1, 2, 3)
+    assert (pr.KEPT, pr.INFO_NOT_PD, pr.BRIDGE, pr.PRUNED) == (0, 1, 2, 3)
+    assert C.sizeof(abi.PruneStats) == C.sizeof(abi.CovSolveStats) + 16 == C.sizeof(abi.SelectStats)
+    assert set(abi.PruneStats().asdict()) >= {"rounds", "endpoints", "prune_seconds", "solve_seconds", "device_seconds", "columns"}
+    for m in ("pruneCandidates", "removeEdges", "pruneEdges"):
+        assert callable(getattr(GraphWrapperHIP, m))
+    hdr = open(os.path.join(ROOT, "include", "spg.h")).read()
+    assert "SPG_PRUNE_BRIDGE = 2" in hdr and "SPG_PRUNE_PRUNED = 3" in hdr and "re-evaluated EVERY round" in hdr and "only shrink" in hdr
+
+
+def test_prune_checks_arguments_before_the_backend():
+    """On an injected (CPU) context: the size queries answer; k = 0 and n = 0 return 0; an index out of range, a non-binary
+    edge, an index listed twice, k < 0, an unknown fixed vertex and an active stepwise marginalisation are SPG_EINVAL with
+    their word; a call that would compute is SPG_ESTATE (no CPU fallback); the Python layer raises."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    sub = _small()
+    ictx = oracle_lib.injected_context()
+    a = GraphWrapperHIP.from_dict(sub, ctx=ictx)
+    ne = a.numEdges()
+    ids = [int(v) for v in sub["ids"][:3]]
+    a.addGLCEdge(ids, np.zeros(3 * 3), np.eye(9))       # edge index ne: not binary
+    L = a.L
+    idx = np.array([0, 2, 5, 7], np.int32)
+    n = len(idx)
+    sel, cl, ck, fl, fm, status = np.zeros(n, np.int32), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+    f = lambda x: x.ctypes.data_as(_f64p)  # noqa: E731
+    i = lambda x: x.ctypes.data_as(_i32p)  # noqa: E731
+    err = lambda: L.spg_last_error(ictx.h).decode()  # noqa: E731
+
+    def prune(ix, cnt, k, cap, fid=-1, h=a.h):
+        return L.spg_graph_prune_candidates(h, fid, i(ix), cnt, k, 0.0, 0.0, 0.0, i(sel), f(cl), f(ck), cap, f(fl), f(fm), i(status), None)
+    assert prune(idx, n, 2, 0) == 2 and prune(idx, n, 2, 1) == 2 and prune(idx, n, 9, 0) == n
+    assert L.spg_graph_prune_candidates(a.h, -1, i(idx), n, 3, 0.0, 0.0, 0.0, None, None, None, 99, None, None, None, None) == 3
+    assert prune(idx, n, 0, n) == 0 and prune(idx, 0, 3, n) == 0
+    st = abi.PruneStats()
+    assert prune(idx, n, 2, 2) == ESTATE and "HIP backend" in err()
+    assert L.spg_graph_prune_candidates(a.h, -1, i(idx), n, n, 0.0, 0.0, 0.0, i(sel), f(cl), f(ck), n, None, None, None, C.byref(st)) == ESTATE
+    for bad, word in ((np.array([0, ne + 1], np.int32), "out of range"), (np.array([0, -1], np.int32), "out of range"),
+                      (np.array([0, ne], np.int32), "not a binary edge"), (np.array([3, 3], np.int32), "listed twice")):
+        assert prune(bad, 2, 1, 1) == EINVAL and word in err() and "candidate 1" in err(), err()
+    assert prune(idx, n, 2, 2, fid=999999) == EINVAL and "fixed vertex" in err()
+    assert prune(idx, n, -1, 2) == EINVAL and "negative" in err()
+    g, which, opts, *_ = util.load_golden("intel_nfr_tree_sp3")
+    sub2, w = util.prefix_graph(g, which, 30)
+    b = GraphWrapperHIP.from_dict(sub2, ctx=ictx)
+    b.begin(w, opts, 0, 1)
+    assert prune(idx, n, 2, 2, h=b.h) == EINVAL and "active" in err()
+    assert L.spg_graph_remove_edges(b.h, i(idx), 1) == EINVAL and "active" in err()
+    with pytest.raises(SpgError, match="HIP backend"):
+        a.pruneCandidates(idx, 2)
+    with pytest.raises(SpgError, match="listed twice"):
+        a.pruneCandidates([1, 1], 1)
+    with pytest.raises(SpgError, match="negative"):
+        a.pruneCandidates(idx, -1)
+    got = a.pruneCandidates(idx, 0)
+    assert len(got["pruned"]) == 0 and len(got["kld"]) == 0 and got["final_loss"].shape == (n,)
+    got = a.pruneCandidates(np.zeros(0, np.int32), 3)
+    assert len(got["pruned"]) == 0 and got["final_margin"].shape == (0,) and got["status"].shape == (0,)
+
+
+def _edge_rows(e):
+    return [(int(e["kind"][k]), tuple(int(v) for v in e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]]),
+             e["data"][e["data_off"][k]:e["data_off"][k + 1]].tobytes()) for k in range(len(e["kind"]))]
+
+
+def test_remove_edges_on_the_host():
+    """spg_graph_remove_edges on an injected context: edges() afterwards is the old list without the removed rows, in
+    order; vertexEdges and the counters follow; duplicate and out-of-range indices leave the graph unchanged; addEdge
+    after a removal works; edges of any kind go."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    sub = _small()
+    ictx = oracle_lib.injected_context()
+    a = GraphWrapperHIP.from_dict(sub, ctx=ictx)
+    ids = [int(v) for v in sub["ids"]]
+    a.addGLCEdge(ids[:3], np.zeros(9), np.eye(9))
+    before = _edge_rows(a.edges())
+    ne = len(before)
+    assert a.numEdges() == ne
+    for bad, word in (([1, 1], "listed twice"), ([0, ne], "out of range"), ([-1], "out of range")):
+        with pytest.raises(SpgError, match=word):
+            a.removeEdges(bad)
+        assert _edge_rows(a.edges()) == before and a.numEdges() == ne
+    a.removeEdges([])
+    assert _edge_rows(a.edges()) == before
+    gone = [5, 0, ne - 1, 2]                                # any order; the last one is the GLC edge
+    a.removeEdges(gone)
+    want = [r for k, r in enumerate(before) if k not in gone]
+    after = a.edges()
+    assert _edge_rows(after) == want and a.numEdges() == ne - 4
+    for v in ids:
+        inc = [k for k, r in enumerate(want) if v in r[1]]
+        assert a.vertexEdges(v).tolist() == inc, v
+    # addEdge after a removal appends; removing it again restores the list
+    rec = sub["edge_data"][0]
+    a.addEdge(int(sub["edge_ij"][0][0]), int(sub["edge_ij"][0][1]), rec[:3], rec[3:])
+    assert _edge_rows(a.edges()) == want + [before[0]] and a.numEdges() == ne - 3
+    a.removeEdges([ne - 4])
+    assert _edge_rows(a.edges()) == want
+
+
+def test_marginalisation_after_a_removal_matches_the_oracle_without_that_edge():
+    """Emulated-stream marginalisation (injected oracle arithmetic) of a graph after removeEdges equals the oracle's
+    marginalisation of the graph built without those edges."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    g, which, opts, *_ = util.load_golden("intel_nfr_tree_sp3")
+    sub, w = util.prefix_graph(g, which, 60)
+    # two loop closures at the current relative pose, inserted at positions 10 and 30 of the edge list
+    poses = {int(i): p for i, p in zip(sub["ids"], sub["poses"])}
+    ids = [int(i) for i in sub["ids"]]
+    extra_ij = np.array([(ids[3], ids[40]), (ids[12], ids[55])], np.int32)
+    extra = np.array([np.concatenate([rr.between(3, poses[int(a)], poses[int(b)]), sub["edge_data"][0, 3:]]) for a, b in extra_ij])
+    loops = [10, 30]
+    plus = dict(sub, edge_ij=np.insert(sub["edge_ij"], [10, 29], extra_ij, axis=0), edge_data=np.insert(sub["edge_data"], [10, 29], extra, axis=0))
+    assert plus["edge_ij"][loops].tolist() == extra_ij.tolist() and len(plus["edge_ij"]) == len(sub["edge_ij"]) + 2
+    ictx = oracle_lib.injected_context()
+    a = GraphWrapperHIP.from_dict(plus, ctx=ictx)
+    a.set_stream_emulation(3)
+    a.removeEdges(loops)
+    st = a.marginalizeNoOptimize(w, opts)
+    og = oracle_lib.OracleGraph.from_dict(sub)
+    assert og.marginalize(w, opts) == 0 and st["n_removed"] == len(w) and st["n_bad_status"] == 0
+    assert util.compare_edge_sets(sub["pose_dim"], og.edges(), a.edges()) <= 1e-9
+
+
+def _build_demo(tmp_path):
+    exe = str(tmp_path / "prune_demo")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "cpp", "prune_demo.cpp"),
+                           "-I" + os.path.join(ROOT, "include"), "-L" + PKG, "-lspg_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_prune_demo_compiles(tmp_path):
+    out = subprocess.run([_build_demo(tmp_path)], capture_output=True, text=True)
+    assert out.returncode == 2 and "usage" in out.stderr
+
+
+# ------------------------------------------------------------------------------------------------------- GPU
+def _add_list(hg, ij, meas, info):
+    """addEdge of the list; returns the edge indices of the added edges (they are appended to edges())"""
+    ne = hg.numEdges()
+    for k, (a, b) in enumerate(ij):
+        hg.addEdge(int(a), int(b), meas[k], info[k])
+    e = hg.edges()
+    idx = np.arange(ne, ne + len(ij), dtype=np.int32)
+    for k, x in enumerate(idx):
+        assert e["vert_ids"][e["vert_off"][x]:e["vert_off"][x + 1]].tolist() == [int(ij[k][0]), int(ij[k][1])]
+    return idx
+
+
+def _check_against(d, ref, single, got, what):
+    """pruned, cond_loss, kld, final_loss, final_margin and status of a device run against a reference run; returns the
+    worst error / bound"""
+    r = len(ref["pruned"])
+    assert np.array_equal(got["pruned"], ref["pruned"]), (what, got["pruned"], ref["pruned"])
+    bounds, kb, worst_star = _bounds(ref, single)
+    worst = 0.0
+    for t in range(r):
+        s = int(ref["pruned"][t])
+        err, tol = abs(got["cond_loss"][t] - ref["cond_loss"][t]), bounds[t][s]
+        kerr = abs(got["kld"][t] - ref["kld"][t])
+        worst = max(worst, err / tol, kerr / kb[t])
+        print(f"{what}: round {t} candidate {s} loss {got['cond_loss'][t]:.12g} error / bound {err / tol:.2e}, kld {got['kld'][t]:.12g} "
+              f"error / bound {kerr / kb[t]:.2e}")
+        assert err <= tol and kerr <= kb[t], (what, t, err, tol, kerr, kb[t])
+    assert np.array_equal(got["status"], ref["status"]), (what, got["status"], ref["status"])
+    live = ~np.isnan(ref["final_loss"])
+    assert np.array_equal(live, ~np.isnan(got["final_loss"])), what
+    if live.any():
+        lam = ref["final_lam"][live]
+        err = np.abs(got["final_loss"][live] - ref["final_loss"][live]) / ((r + 1) * single[live] / (lam * worst_star))
+        merr = np.abs(got["final_margin"][live] - ref["final_margin"][live]) / ((r + 1) * (2 * single[live] / d) / (lam ** 2 * worst_star))
+        print(f"{what}: final losses, worst error / bound {err.max():.2e}; final margins {merr.max():.2e}")
+        worst = max(worst, float(err.max()), float(merr.max()))
+        assert err.max() <= 1.0 and merr.max() <= 1.0, (what, err.max(), merr.max())
+    return worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,n", CASES)
+def test_sequence_and_values_on_constructed_lists(case, n, hip_ctx):
+    """The 40 constructed edges are added with addEdge and are the candidates, k = 8, before and after the case's
+    marginalisation, both gauges: the reference's sequence exactly, cond_loss[t], kld[t], final_loss and
+    final_margin within their bounds, the statuses, the stats; the added edges are removed again with removeEdges between
+    the gauges. Measured on an MI355X, worst error / bound: see DESIGN 7."""
+    from tests.test_relative_covariance import _small_graphs
+    sub, graphs, kept = _small_graphs(case, n, hip_ctx)
+    d = sub["pose_dim"]
+    worst, lead = 0.0, np.inf
+    for hg, og in graphs:
+        ids = [int(i) for i in hg.vertices()[0]]
+        for fid in _fids(ids, kept):
+            H0 = og.information(fid)
+            ij, meas, info, rank, T, H1, Sig1 = _problem(d, hg, fid, H0)
+            ref = pr.greedy_sigma(Sig1, T, [True] * N_ADD, K)
+            single = _single_bounds(d, T, Sig1)
+            lead = min(lead, _lead(ref, _bounds(ref, single)[0]))
+            before = _edge_rows(hg.edges())
+            idx = _add_list(hg, ij, meas, info)
+            got = hg.pruneCandidates(idx, K, fixed_id=fid)
+            what = f"{case}[{n}] {'after' if hg is graphs[1][0] else 'before'} fixed {fid}"
+            worst = max(worst, _check_against(d, ref, single, got, what))
+            s = hg.last_covariance_stats
+            assert s["rounds"] == K and 0 < s["prune_seconds"] < s["device_seconds"]
+            assert s["endpoints"] == len({int(v) for v in ij.ravel()} - {fid})
+            hg.removeEdges(idx)
+            assert _edge_rows(hg.edges()) == before
+    print(f"{case}[{n}]: worst error / bound {worst:.2e}, smallest lead / (10 bounds) {lead:.2e}")
+
+
+def _binary_edges(hg):
+    e = hg.edges()
+    idx = np.flatnonzero(e["kind"] == abi.EDGE_BINARY).astype(np.int32)
+    ij = np.array([e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]] for k in idx], np.int32).reshape(-1, 2)
+    data = np.array([e["data"][e["data_off"][k]:e["data_off"][k + 1]] for k in idx])
+    return idx, ij, data, bool((e["kind"] != abi.EDGE_BINARY).any())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,n", CASES)
+def test_round_zero_losses_margins_and_bridges_of_real_edges(case, n, hip_ctx):
+    """Candidates: every binary edge of the graph (before and after the marginalisation, first gauge). With max_loss below
+    every loss nothing is pruned and final_loss / final_margin are the round-0 values: they match numpy on inv(information())
+    within bound_i(0) and the margin bound wherever numpy's margin is >= 1e-4; the BRIDGE statuses are exactly the
+    edges whose numpy margin is below 1e-6, and on graphs of binary edges alone exactly the bridges found by connectivity.
+    With k = 1 exactly one edge goes and it is no bridge. No sequence is asserted. The device's worst bridge margin and
+    smallest non-bridge margin are printed."""
+    from tests.test_relative_covariance import _small_graphs
+    sub, graphs, kept = _small_graphs(case, n, hip_ctx)
+    d, ps = sub["pose_dim"], abi.pose_stride(sub["pose_dim"])
+    for hg, og in graphs:
+        ids = [int(i) for i in hg.vertices()[0]]
+        fid = ids[0]
+        idx, ij, data, nary = _binary_edges(hg)
+        Sig = np.linalg.inv(og.information(fid))
+        T = sr.terms(d, _poses(hg), _at(ids, fid), ij, data[:, :ps], data[:, ps:])
+        single = _single_bounds(d, T, Sig)
+        ref = pr.greedy_sigma(Sig, T, [t["ok"] for t in T], 0)
+        got = hg.pruneCandidates(idx, 1, max_loss=1e-300, fixed_id=fid)
+        assert len(got["pruned"]) == 0 and hg.last_covariance_stats["rounds"] == 0
+        ref_bridge = ~(ref["final_margin"] >= 1e-6)
+        dev_bridge = got["status"] == abi.PRUNE_BRIDGE
+        worst_b = np.abs(got["final_margin"][dev_bridge]).max() if dev_bridge.any() else 0.0
+        least = got["final_margin"][~dev_bridge].min()
+        print(f"{case}[{n}] {'after' if hg is graphs[1][0] else 'before'}: {dev_bridge.sum()} bridges of {len(idx)} edges, worst bridge margin "
+              f"{worst_b:.2e}, smallest non-bridge margin {least:.2e} (numpy {ref['final_margin'][~ref_bridge].min():.2e})")
+        assert np.array_equal(dev_bridge, ref_bridge) and np.all(got["status"][~dev_bridge] == abi.PRUNE_KEPT)
+        if not nary:
+            at = {v: k for k, v in enumerate(ids)}
+            assert np.flatnonzero(dev_bridge).tolist() == pr.connectivity_bridges(len(ids), [(at[int(a)], at[int(b)]) for a, b in ij])
+        sure = ref["final_margin"] >= 1e-4
+        lam = ref["final_lam"]
+        merr = np.abs(got["final_margin"][sure] - ref["final_margin"][sure]) / (2 * single[sure] / d / lam[sure] ** 2)
+        print(f"  margins: worst error / bound {merr.max():.2e}")
+        assert merr.max() <= 1.0
+        if not nary:
+            lerr = np.abs(got["final_loss"][sure] - ref["final_loss"][sure]) / (single[sure] / lam[sure])
+            print(f"  losses: worst error / bound {lerr.max():.2e}")
+            assert lerr.max() <= 1.0
+        one = hg.pruneCandidates(idx, 1, fixed_id=fid)
+        assert len(one["pruned"]) == 1 and not ref_bridge[one["pruned"][0]] and one["kld"][0] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,n", CASES)
+def test_kld_and_log_det_identities_through_prune_edges(case, n, hip_ctx):
+    """Independent of prune_ref's loop: pruneEdges on a clone (the constructed list, k = 8); kld[-1] equals the original's
+    kullbackLeibler with the pruned clone as `other` (same fixed vertex, estimates untouched), and the sum of cond_loss
+    equals 1/2 (ln det information() before - after), both within the summed bounds plus 1e-12 |ln det H|. The inverse
+    relation with the selection: selectCandidates picks k edges, addEdge adds them, and pruneCandidates restricted to those
+    with k = 1 has as its smallest loss the last selected edge's cond_gain, within the sum of the two bounds."""
+    from tests.test_relative_covariance import _small_graphs
+    sub, graphs, kept = _small_graphs(case, n, hip_ctx)
+    d = sub["pose_dim"]
+    worst = [0.0, 0.0, 0.0]
+    for hg, og in graphs:
+        ids = [int(i) for i in hg.vertices()[0]]
+        fid = _fids(ids, kept)[0]
+        H0 = og.information(fid)
+        ij, meas, info, rank, T, H1, Sig1 = _problem(d, hg, fid, H0)
+        single = _single_bounds(d, T, Sig1)
+        ref = pr.greedy_sigma(Sig1, T, [True] * N_ADD, K)
+        bounds, kb, _ = _bounds(ref, single)
+        # the inverse relation first, on the graph without the list: select 4 of the eight graded candidates (the strongest
+        # four, strongest first), add them, prune one: the weakest of the four, the last selected, at the loss = its gain
+        few = 4
+        graded = np.flatnonzero(rank < K)
+        sel = hg.selectCandidates(ij[graded], meas[graded], info[graded], few, fixed_id=fid)
+        single0 = _single_bounds(d, [T[i] for i in graded], np.linalg.inv(H0))
+        before = _edge_rows(hg.edges())
+        chosen = graded[sel["selected"]]
+        idx = _add_list(hg, ij[chosen], meas[chosen], info[chosen])
+        back = hg.pruneCandidates(idx, 1, fixed_id=fid)
+        # the prune's M is the inverse of the select's: lambda_min(M) >= det M = exp(-2 gain); covariances only shrank by the additions
+        s0 = single0[sel["selected"][-1]]
+        tol = few * s0 + s0 * np.exp(2.0 * sel["cond_gain"][-1])
+        err = abs(back["cond_loss"][0] - sel["cond_gain"][-1])
+        worst[2] = max(worst[2], err / tol)
+        assert back["pruned"].tolist() == [few - 1] and err <= tol, (case, back["pruned"], back["cond_loss"], sel["cond_gain"], tol)
+        assert back["cond_loss"][0] <= np.nanmin(back["final_loss"])
+        hg.removeEdges(idx)
+        assert _edge_rows(hg.edges()) == before
+        # the identities
+        idx = _add_list(hg, ij, meas, info)
+        clone = hg.clonePortion(max(ids), optimize=False)
+        assert clone.numEdges() == hg.numEdges()
+        got = clone.pruneEdges(idx, K, fixed_id=fid)
+        assert len(got["pruned"]) == K and clone.numEdges() == hg.numEdges() - K
+        Hb, Ha = hg.information(fid), clone.information(fid)
+        ld0, ld1 = np.linalg.slogdet(Hb)[1], np.linalg.slogdet(Ha)[1]
+        slack = 1e-12 * (abs(ld0) + abs(ld1))
+        allowed = sum(bounds[t][int(s)] for t, s in enumerate(ref["pruned"])) + slack
+        err = abs(got["cond_loss"].sum() - 0.5 * (ld0 - ld1))
+        worst[0] = max(worst[0], err / allowed)
+        assert err <= allowed, (case, got["cond_loss"].sum(), 0.5 * (ld0 - ld1), allowed)
+        kld = hg.kullbackLeibler(clone, fixed_id=fid)
+        kerr = abs(got["kld"][-1] - kld)
+        worst[1] = max(worst[1], kerr / (kb[-1] + slack))
+        assert kerr <= kb[-1] + slack, (case, got["kld"][-1], kld, kb[-1])
+        hg.removeEdges(idx)
+    print(f"{case}[{n}]: deviation / allowed: sum of losses {worst[0]:.2e}, kld against kullbackLeibler {worst[1]:.2e}, inverse of select {worst[2]:.2e}")
+
+
+@pytest.mark.gpu
+def test_stop_rules_sizes_and_the_cycle(hip_ctx):
+    """synth_manhattan(400) with 300 added far-pair edges as candidates (two workgroups of argmin partials), graded so that
+    the order is decided: the reference's first five; max_loss between the third and fourth loss stops after three; max_kld
+    between two cumulative values stops at the earlier round; k > n; n = 1; an edge to the fixed vertex; a candidate whose
+    Omega is indefinite (addEdge accepts the record) is INFO_NOT_PD and never pruned; the 4-cycle: one edge goes, three
+    become bridges."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    g = g2o_io.synth_manhattan(n_poses=400, side=20)
+    hg = GraphWrapperHIP.from_dict(g, ctx=hip_ctx)
+    ids = [int(i) for i in hg.vertices()[0]]
+    fid = ids[0]
+    d = 3
+    far, meas, info, T, ok, H1 = _manhattan_list(hg, fid, _oracle_of(hg).information(fid))
+    idx = _add_list(hg, far, meas, info)
+    Sig1 = np.linalg.inv(H1)
+    single = _single_bounds(d, T, Sig1)
+    single[7] = np.inf
+    ref = pr.greedy_sigma(Sig1, T, ok, 5)
+    assert ref["pruned"].tolist() == [0, 1, 2, 3, 4]
+    got = hg.pruneCandidates(idx, 5, fixed_id=fid)
+    _check_against(d, ref, single, got, "manhattan 300")
+    assert got["status"][7] == abi.PRUNE_INFO_NOT_PD and np.isnan(got["final_loss"][7]) and np.isnan(got["final_margin"][7])
+    assert got["status"][5] == abi.PRUNE_KEPT and np.isfinite(got["final_loss"][5])
+    mid = 0.5 * (ref["cond_loss"][2] + ref["cond_loss"][3])
+    got3 = hg.pruneCandidates(idx, 5, max_loss=mid, fixed_id=fid)
+    assert got3["pruned"].tolist() == [0, 1, 2] and hg.last_covariance_stats["rounds"] == 3 and (got3["status"] == abi.PRUNE_PRUNED).sum() == 3
+    _check_against(d, pr.greedy_sigma(Sig1, T, ok, 5, max_loss=mid), single, got3, "manhattan 300, max_loss")
+    midk = 0.5 * (ref["kld"][1] + ref["kld"][2])
+    gotk = hg.pruneCandidates(idx, 5, max_kld=midk, fixed_id=fid)
+    assert gotk["pruned"].tolist() == [0, 1] and np.array_equal(gotk["kld"], got["kld"][:2])
+    # k > n: every usable candidate goes (far-pair edges are never bridges), then nothing is left
+    few = idx[[5, 6, 7, 8, 9]]
+    gotn = hg.pruneCandidates(few, 9, fixed_id=fid)
+    assert len(gotn["pruned"]) == 4 and sorted(gotn["pruned"].tolist()) == [0, 1, 3, 4] and np.array_equal(gotn["status"], [3, 3, 1, 3, 3])
+    assert np.all(np.isnan(gotn["final_loss"])) and np.all(np.diff(gotn["kld"]) > 0)
+    # n = 1, and the edge to the fixed vertex alone
+    got1 = hg.pruneCandidates(idx[:1], 1, fixed_id=fid)
+    assert got1["pruned"].tolist() == [0] and abs(got1["cond_loss"][0] - ref["cond_loss"][0]) <= _bounds(ref, single)[0][0][0]
+    gotf = hg.pruneCandidates(idx[5:6], 1, fixed_id=fid)
+    assert gotf["pruned"].tolist() == [0] and abs(gotf["cond_loss"][0] - ref["rounds"][0][5][0]) <= _bounds(ref, single)[0][0][5]
+    # the 4-cycle
+    for cyc, decided in ((_cycle_graph(), False), (_tie_free_cycle(), True)):
+        cg = GraphWrapperHIP.from_dict(cyc, ctx=hip_ctx)
+        Tc, Hc = _cycle_reference(cyc)
+        refc = pr.greedy_sigma(np.linalg.inv(Hc), Tc, [True] * 4, 4)
+        gotc = cg.pruneEdges(np.arange(4, dtype=np.int32), 4, fixed_id=0)
+        assert len(gotc["pruned"]) == 1 and cg.numEdges() == 3
+        if decided:
+            assert gotc["pruned"].tolist() == refc["pruned"].tolist()
+            assert abs(gotc["cond_loss"][0] - refc["cond_loss"][0]) <= 1e-9 and abs(gotc["kld"][0] - refc["kld"][0]) <= 1e-9
+        want = np.full(4, abi.PRUNE_BRIDGE)
+        want[gotc["pruned"][0]] = abi.PRUNE_PRUNED
+        assert np.array_equal(gotc["status"], want) and np.all(np.isnan(gotc["final_loss"]))
+        rest = np.arange(4) != gotc["pruned"][0]
+        assert np.all(np.abs(gotc["final_margin"][rest]) < 1e-8) and np.isnan(gotc["final_margin"][~rest]).all()
+        # every edge of the path that is left is a bridge: nothing more can go
+        again = cg.pruneCandidates(np.arange(3, dtype=np.int32), 3, fixed_id=0)
+        assert len(again["pruned"]) == 0 and np.all(again["status"] == abi.PRUNE_BRIDGE)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", [3, 6])
+def test_pruning_leaves_the_graph_and_the_other_calls_untouched(d, hip_ctx):
+    """pruneCandidates does not modify the graph: the edges, the estimates and the outputs of pairCovariances,
+    relativeCovariances, scoreCandidates and selectCandidates are bit-identical before and after it."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    from tests.test_relative_covariance import _gate_candidates, _gate_graph
+    g = _gate_graph(d)
+    hg = GraphWrapperHIP.from_dict(g, ctx=hip_ctx)
+    fid = int(g["ids"][0])
+    ij, meas, info, _ = _gate_candidates(d, g)
+    ij, meas, info = ij[:40], meas[:40], info[:40]
+    epairs = np.ascontiguousarray(g["edge_ij"][:50], np.int32)
+
+    def calls():
+        out = dict(hg.scoreCandidates(ij, meas, info, fixed_id=fid))
+        out.update({"sel_" + k: v for k, v in hg.selectCandidates(ij, meas, info, 4, fixed_id=fid).items()})
+        out["rel"], out["relcov"] = hg.relativeCovariances(ij, fixed_id=fid)
+        out["pair"] = hg.pairCovariances(epairs, fixed_id=fid)
+        return out
+    before, e0, v0 = calls(), hg.edges(), hg.vertices()
+    got = hg.pruneCandidates(np.arange(0, hg.numEdges(), 7, dtype=np.int32), 5, fixed_id=fid)
+    assert len(got["pruned"]) == 5 and np.all(got["cond_loss"] > 0) and np.all(np.diff(got["kld"]) > 0)
+    after, e1, v1 = calls(), hg.edges(), hg.vertices()
+    for k in e0:
+        assert np.array_equal(e0[k], e1[k]), k
+    assert np.array_equal(v0[0], v1[0]) and np.array_equal(v0[1], v1[1])
+    for k in before:
+        assert np.array_equal(before[k], after[k], equal_nan=True), k
+
+
+@pytest.mark.gpu
+def test_cpp_facade_pruning_matches_python(tmp_path, hip_ctx):
+    """tests/cpp/prune_demo.cpp prunes 6 of every third edge of a small sphere through the façade and removes them; the
+    indices, losses and KLD equal the Python binding's bit for bit."""
+    from sparsifyposegraph_amd.graph import GraphWrapperHIP
+    g = g2o_io.synth_sphere(n_poses=200, ring=20)
+    path = str(tmp_path / "s200.g2o")
+    g2o_io.write_g2o(path, g)
+    out = subprocess.run([_build_demo(tmp_path), path, "6", str(tmp_path / "cpp.txt")], capture_output=True, text=True)
+    assert out.returncode == 0 and "pruning ok" in out.stdout, out.stdout + out.stderr
+    cpp = np.loadtxt(str(tmp_path / "cpp.txt")).reshape(-1, 3)
+    hg = GraphWrapperHIP.load(path, ctx=hip_ctx)
+    got = hg.pruneCandidates(np.arange(0, hg.numEdges(), 3, dtype=np.int32), 6)
+    assert len(cpp) == 6 and np.array_equal(cpp[:, 0].astype(np.int32), got["pruned"])
+    assert np.array_equal(cpp[:, 1], got["cond_loss"]) and np.array_equal(cpp[:, 2], got["kld"])

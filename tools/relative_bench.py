@@ -4,11 +4,17 @@ the current relative pose, Omega = the generator's info_diag), relativeCovarianc
 
     python tools/relative_bench.py [--mode score|relative|pairs] [--poses 100000] [--ring 400] [--vertex 50000] [--runs 5]
     python tools/relative_bench.py --mode select --k K --candidates N [--endpoints 7000]
+    python tools/relative_bench.py --mode prune --k K --candidates N --endpoints M
 
 --mode select: selectCandidates of N random pairs without a common edge, drawn over a random pool of at most --endpoints
 (at most 7 000) vertices, Omega of an existing edge, z = the current relative pose plus noise; select_seconds, rounds and
 endpoints are those of spg_select_stats. The same process also times one scoreCandidates call of the same list
 (score_device_seconds): k of those, plus k addEdge and the round trips, is what the selection replaces.
+
+--mode prune: pruneCandidates of up to N existing edges whose endpoints both fall in a block of M consecutive vertices
+(every edge inside the block, at most N of them); prune_seconds, rounds and endpoints are those of spg_prune_stats. The
+same process times selectCandidates at the same k on a list with the same endpoint pairs (z = the current relative pose
+plus noise, Omega of an existing edge), so the column-solve part is the same and select_seconds stands beside prune_seconds.
 
 device_seconds and solve_seconds are those of spg_cov_solve_stats (HIP events: factorisation, column solves, selected
 inverse, assembly and, for score / relative, sp_relative_kernel); wall_seconds is the host clock around the whole call
@@ -29,7 +35,7 @@ from sparsifyposegraph_amd.graph import GraphWrapperHIP  # noqa: E402
 from sparsifyposegraph_amd.lib import Context  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=("score", "relative", "pairs", "select"), default="score")
+ap.add_argument("--mode", choices=("score", "relative", "pairs", "select", "prune"), default="score")
 ap.add_argument("--k", type=int, default=10)
 ap.add_argument("--candidates", type=int, default=2000)
 ap.add_argument("--endpoints", type=int, default=7000)
@@ -55,6 +61,43 @@ if args.mode == "select":
         if (min(a, b), max(a, b)) not in adj:
             far.append((a, b))
     star = np.array(far, np.int32)
+if args.mode == "prune":
+    lo = max(0, min(args.vertex, len(ids) - args.endpoints))
+    pool = {int(v) for v in ids[lo:lo + args.endpoints]}
+    e = hg.edges()
+    inside = [k for k in range(len(e["kind"])) if all(int(v) in pool for v in e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]])]
+    eidx = np.array(inside[:args.candidates], np.int32)
+    star = np.array([e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]] for k in eidx], np.int32)
+    rng = np.random.default_rng(2024)
+    meas = hg.relativeCovariances(star)[0]
+    meas[:, :3] += 0.01 * rng.normal(size=(len(star), 3))
+    info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
+
+    def timed(fn, key):
+        fn()   # warm-up
+        out = {"device": [], "solve": [], "wall": [], key: []}
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            r = fn()
+            out["wall"].append(time.perf_counter() - t0)
+            st = hg.last_covariance_stats
+            out["device"].append(st["device_seconds"]); out["solve"].append(st["solve_seconds"]); out[key].append(st[key])
+        return r, st, out
+    rp, sp, tp = timed(lambda: hg.pruneCandidates(eidx, args.k), "prune_seconds")
+    rs, ss, ts = timed(lambda: hg.selectCandidates(star, meas, info, args.k), "select_seconds")
+    med = statistics.median
+    print(json.dumps({
+        "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {len(eidx)} existing edges inside a block of {len(pool)} vertices",
+        "mode": "prune", "k": args.k, "candidates": len(eidx), "runs": args.runs, "rounds": sp["rounds"], "endpoints": sp["endpoints"],
+        "prune_seconds": med(tp["prune_seconds"]), "prune_seconds_min": min(tp["prune_seconds"]), "prune_seconds_max": max(tp["prune_seconds"]),
+        "device_seconds": med(tp["device"]), "device_seconds_min": min(tp["device"]), "device_seconds_max": max(tp["device"]),
+        "solve_seconds": med(tp["solve"]), "wall_seconds": med(tp["wall"]), "columns": sp["columns"], "rhs_batches": sp["rhs_batches"],
+        "kld": float(rp["kld"][-1]) if len(rp["kld"]) else 0.0, "bridges": int((rp["status"] == 2).sum()),
+        "select_rounds": ss["rounds"], "select_endpoints": ss["endpoints"], "select_seconds": med(ts["select_seconds"]),
+        "select_seconds_min": min(ts["select_seconds"]), "select_seconds_max": max(ts["select_seconds"]),
+        "select_device_seconds": med(ts["device"]), "select_solve_seconds": med(ts["solve"]), "select_wall_seconds": med(ts["wall"]),
+        "select_columns": ss["columns"], "prune_over_select": med(tp["prune_seconds"]) / med(ts["select_seconds"])}), flush=True)
+    sys.exit(0)
 info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
 meas = None
 if args.mode == "select":
