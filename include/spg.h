@@ -476,7 +476,8 @@ int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij
  * when the best conditional gain is < min_gain.
  * The joint covariance of the m distinct non-fixed endpoints (m D x m D, each unordered pair solved once, as
  * spg_graph_joint_marginal_covariance) and a history of min(k, n) D^2 doubles per candidate stay on the device: m D above
- * 46 000, or a joint block and history beyond free HBM, are SPG_ECAPACITY before anything runs. a or b may be the fixed
+ * 46 000, or a joint block and history beyond free HBM, are SPG_ECAPACITY before anything runs (the default method,
+ * SPG_GREEDY_JOINT; spg_ctx_set_greedy_method below lifts the bound with SPG_GREEDY_LAZY). a or b may be the fixed
  * vertex, a pair may be listed many times, the graph is not modified and its robust kernel is ignored. An unknown id,
  * a == b, a non-finite measurement, an unknown fixed vertex, k < 0 and an active stepwise marginalisation are SPG_EINVAL
  * (the text names the pair) before the backend is touched; SPG_ESTATE without HIP. */
@@ -521,7 +522,7 @@ int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const int32_t *i
  * is the exact KLD of the pruned graph against the original at the same estimates: what spg_graph_kullback_leibler on the
  * original with the pruned graph as `other` returns, 1/2 (tr(H_p Sigma) - N + ln det H - ln det H_p), mean term 0.
  * Memory and SPG_ECAPACITY exactly as spg_graph_select_candidates (joint covariance of the distinct non-fixed endpoints,
- * min(k, n) D^2 doubles of history per candidate). An endpoint may be the fixed vertex. The graph is NOT modified: apply
+ * min(k, n) D^2 doubles of history per candidate; spg_ctx_set_greedy_method below). An endpoint may be the fixed vertex. The graph is NOT modified: apply
  * the result with spg_graph_remove_edges. An index out of range, a non-binary edge (GLC, MULTI), an index listed twice,
  * k < 0, an unknown fixed vertex and an active stepwise marginalisation are SPG_EINVAL (the text names the candidate)
  * before the backend is touched; SPG_ESTATE without HIP. */
@@ -542,6 +543,38 @@ int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ed
                                double max_loss, double max_kld, double min_margin,
                                int32_t *pruned, double *cond_loss, double *kld, int cap,
                                double *final_loss, double *final_margin, int32_t *status, spg_prune_stats *stats);
+/* ---- how the two greedy calls above get at Sigma ------------------------------------------------------------
+ * SPG_GREEDY_JOINT (default): the m D x m D joint block described above, and its 46 000 bound.
+ * SPG_GREEDY_LAZY: no joint block, and no bound on m D. Round 0 comes from one 2D x 2D block per distinct ordered endpoint
+ *   pair (the blocks of spg_graph_relative_covariances: every prune candidate is an edge, so its block is read from the
+ *   selected inverse without a column solve). Each round then solves, on the factor, the D columns of Sigma at the two
+ *   endpoints of the candidate it chose, in one 64-wide right-hand-side panel, and keeps them in a column cache on the
+ *   device: one strip Sigma[S, v] (m D x D) per cached vertex. Columns belong to the original Sigma and never go stale.
+ *   The rest of the panel is filled with the endpoint columns of the next-best candidates. The selected inverse overwrites
+ *   the factor, so a lazy call factorises a second time after round 0 (`refactorised`). What must fit in free HBM (1 GB
+ *   kept free), else SPG_ECAPACITY with the sizes in the text: the pair blocks, the histories, one panel workspace and at
+ *   least two strips; the cache takes what is left, at most m strips and at most what min(k, n) rounds can fill. Results are those of JOINT within rounding: the same
+ *   recurrence on blocks that come from column solves instead of the joint block's mix of both.
+ * SPG_GREEDY_AUTO: JOINT whenever JOINT would not return SPG_ECAPACITY (m D <= 46 000 and joint block + histories
+ *   within free HBM), else LAZY. A capacity rule only.
+ * lookahead: candidates whose endpoint columns one panel may hold, the chosen one included. 0 = a full panel, 64 / 2D
+ *   (5 for SE3, 10 for SE2); 1 = the chosen candidate only; larger values are clamped. lookahead < 0 or an unknown method
+ *   is SPG_EINVAL. Signatures, eligibility, gate, stop rules, tie order, statuses and the kld definition of the two calls
+ *   are the same in every mode. */
+enum { SPG_GREEDY_JOINT = 0, SPG_GREEDY_LAZY = 1, SPG_GREEDY_AUTO = 2 };
+int spg_ctx_set_greedy_method(spg_ctx *ctx, int method, int lookahead);
+typedef struct {
+    int32_t method, lookahead;       /* the method used (JOINT or LAZY) and, for LAZY, the candidates per panel (else 0) */
+    int32_t rounds, refactorised;    /* rounds run; 1 when the factor was rebuilt after the selected inverse */
+    int64_t column_vertices;         /* vertices whose columns were solved during the rounds, speculative ones included */
+    int64_t column_hits;             /* endpoint columns of a chosen candidate that were already cached */
+    int32_t rhs_batches, evictions;  /* panels swept during the rounds; strips given up for a needed column */
+    double round_solve_seconds;      /* HIP-event time of the per-round sweeps */
+    double cache_bytes;              /* size of the column cache */
+} spg_greedy_stats;
+/* of the context's last spg_graph_select_candidates / _prune_candidates call that reached the device (all zero before) */
+int spg_ctx_greedy_stats(spg_ctx *ctx, spg_greedy_stats *out);
+
 /* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is
  * canonicalised first, as spg_graph_get_edges does). Survivors keep their relative order. Bridges may be removed: a
  * disconnected graph later shows as SPG_ENOTPD. An index out of range or listed twice and an active stepwise

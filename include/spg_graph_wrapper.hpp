@@ -289,6 +289,12 @@ public:
     // rel_tol == 0 with max_cycles > 0 = exactly that many cycles
     void setFactorDescentParams(double rel_tol, int max_cycles) { check(spg_ctx_set_factor_descent(_ctx->h, rel_tol, max_cycles), "spg_ctx_set_factor_descent"); }
     spg_pcg_stats pcgStats() const { spg_pcg_stats st{}; check(spg_ctx_pcg_stats(_ctx->h, &st), "spg_ctx_pcg_stats"); return st; }
+    // How selectCandidates / pruneCandidates / pruneEdges of this wrapper's context get at Sigma (spg_ctx_set_greedy_method
+    // in include/spg.h): the joint block of all endpoints (default, at most 46 000 variables), covariance columns solved
+    // round by round (no bound), or JOINT where it fits and LAZY beyond. lookahead: candidates per panel, 0 = a full panel.
+    enum GreedyMethod { GreedyJoint = SPG_GREEDY_JOINT, GreedyLazy = SPG_GREEDY_LAZY, GreedyAuto = SPG_GREEDY_AUTO };
+    void setGreedyMethod(int method, int lookahead = 0) { check(spg_ctx_set_greedy_method(_ctx->h, method, lookahead), "spg_ctx_set_greedy_method"); }
+    spg_greedy_stats greedyStats() const { spg_greedy_stats st{}; check(spg_ctx_greedy_stats(_ctx->h, &st), "spg_ctx_greedy_stats"); return st; }
     GraphWrapperHIP(const GraphWrapperHIP &) = delete;
     GraphWrapperHIP &operator=(const GraphWrapperHIP &) = delete;
     ~GraphWrapperHIP() override {

@@ -132,6 +132,20 @@ class PruneStats(C.Structure):
         return d
 
 
+# SPG_GREEDY_* (include/spg.h): how spg_graph_select_candidates / _prune_candidates get at Sigma, spg_ctx_set_greedy_method
+GREEDY_JOINT, GREEDY_LAZY, GREEDY_AUTO = 0, 1, 2
+
+
+class GreedyStats(C.Structure):
+    """spg_greedy_stats (include/spg.h)"""
+    _fields_ = [("method", C.c_int32), ("lookahead", C.c_int32), ("rounds", C.c_int32), ("refactorised", C.c_int32),
+                ("column_vertices", C.c_int64), ("column_hits", C.c_int64), ("rhs_batches", C.c_int32), ("evictions", C.c_int32),
+                ("round_solve_seconds", C.c_double), ("cache_bytes", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OptimizeStats(C.Structure):
     """spg_optimize_stats (include/spg.h)"""
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double),

@@ -128,6 +128,9 @@ struct spg_ctx {
     double pcg_rel_tol = 0;       // spg_ctx_set_pcg; <= 0: the defaults (1e-10, min(n, 20000))
     int pcg_max_iter = 0;
     spg_pcg_stats pcg_stats{};    // of the last optimize call
+    int greedy_method = 0;        // SPG_GREEDY_*: how select / prune get at Sigma (spg_ctx_set_greedy_method)
+    int greedy_lookahead = 0;     // candidates per panel of the lazy rounds; 0: a full panel
+    spg_greedy_stats greedy_stats{};   // of the last select / prune call that reached the device
     spg::StreamPort *sim_port = nullptr;   // tools/host_sim.cpp only: a simulated persistent worker behind an injected backend
     char err[768] = {0};
 };

@@ -123,6 +123,17 @@ extern "C" int spg_ctx_pcg_stats(spg_ctx *c, spg_pcg_stats *out) {
     *out = c->pcg_stats;
     return 0;
 }
+extern "C" int spg_ctx_set_greedy_method(spg_ctx *c, int method, int lookahead) {
+    if (!c || method < SPG_GREEDY_JOINT || method > SPG_GREEDY_AUTO || lookahead < 0) return SPG_EINVAL;
+    c->greedy_method = method;
+    c->greedy_lookahead = lookahead;
+    return 0;
+}
+extern "C" int spg_ctx_greedy_stats(spg_ctx *c, spg_greedy_stats *out) {
+    if (!c || !out) return SPG_EINVAL;
+    *out = c->greedy_stats;
+    return 0;
+}
 
 extern "C" int spg_ctx_rank(const spg_ctx *c) { return c ? c->rank : 0; }
 extern "C" int spg_ctx_nranks(const spg_ctx *c) { return c ? c->nranks : 0; }

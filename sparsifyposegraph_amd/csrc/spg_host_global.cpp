@@ -533,6 +533,31 @@ extern "C" int spg_graph_score_candidates(spg_graph *g, int32_t fixed_id, const 
 
 // ================================================================================= greedy candidate selection
 namespace {
+// Round-0 state of the lazy greedy calls: one 2D x 2D block per distinct ordered pair of vertex indices, the list
+// relative_call builds (sub-block lists of cov_solve_device, row stride 2D), and per candidate the slot of its block.
+struct PairBlocks {
+    std::vector<int32_t> va, vb, slot;
+    std::vector<int64_t> dst;
+    std::unordered_map<uint64_t, int32_t> slot_of;
+    void add(int32_t ia, int32_t ib, int D) {
+        const int64_t W = 2 * D;
+        auto it = slot_of.emplace(((uint64_t)(uint32_t)ia << 32) | (uint32_t)ib, (int32_t)slot_of.size());
+        if (it.second) {
+            const int32_t v[2] = {ia, ib};
+            const int64_t u = it.first->second;
+            for (int ka = 0; ka < 2; ka++)
+                for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(u * W * W + ka * D * W + kb * D); }
+        }
+        slot.push_back(it.first->second);
+    }
+    int64_t len(int D) const { return (int64_t)slot_of.size() * 4 * D * D; }
+};
+// spg_ctx_greedy_stats after a call that took the joint block
+void joint_greedy_stats(spg_ctx *c, int rounds) {
+    c->greedy_stats = spg_greedy_stats{};
+    c->greedy_stats.method = SPG_GREEDY_JOINT;
+    c->greedy_stats.rounds = rounds;
+}
 // spg_graph_select_candidates: the checks of relative_call, then the endpoint set S (distinct non-fixed endpoints in
 // first-appearance order), the sub-block list of its m x m joint covariance as spg_graph_joint_marginal_covariance builds
 // it, and per candidate the slots of its endpoints in S (-1 = the fixed vertex).
@@ -565,26 +590,46 @@ int select_call(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double 
     const int kk = std::min(k, n);
     if (kk == 0) return 0;
     const int64_t m = (int64_t)S.size(), W = m * D, need = W * W;
-    if (W > 46000) {
+    const int method = g->ctx->greedy_method;
+    if (method == SPG_GREEDY_JOINT && W > 46000) {
         snprintf(g->ctx->err, sizeof g->ctx->err, "%s: %lld distinct endpoints, limited to 46k variables, the bound of spg_graph_joint_marginal_covariance",
                  what, (long long)m);
         return SPG_ECAPACITY;
     }
     if (!selected || !cond_gain || cap < kk) return kk;
-    std::vector<int32_t> va, vb;
-    std::vector<int64_t> dst;
-    va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
-    for (int64_t a = 0; a < m; a++)
-        for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
-    DenseStage st;
     spg_select_stats ss{};
     ss.endpoints = (int32_t)m;
-    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
-    if (staged < 0) return staged;
     int nsel = 0;
-    if (int rc = spg::hip_sparse_select(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
-                                        ca.data(), cb.data(), sa.data(), sb.data(), n, records, kk, min_gain, max_d2, selected, cond_gain, final_gain,
-                                        status, &nsel, ss, g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (method == SPG_GREEDY_JOINT || (method == SPG_GREEDY_AUTO && W <= 46000)) {
+        std::vector<int32_t> va, vb;
+        std::vector<int64_t> dst;
+        va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
+        for (int64_t a = 0; a < m; a++)
+            for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
+        DenseStage st;
+        const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
+        if (staged < 0) return staged;
+        const int rc = spg::hip_sparse_select(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
+                                              ca.data(), cb.data(), sa.data(), sb.data(), n, records, kk, min_gain, max_d2, selected, cond_gain, final_gain,
+                                              status, &nsel, ss, g->ctx->err, sizeof g->ctx->err);
+        if (rc == 0) {
+            joint_greedy_stats(g->ctx, ss.rounds);
+            if (stats) *stats = ss;
+            return nsel;
+        }
+        if (!(method == SPG_GREEDY_AUTO && rc == SPG_ECAPACITY)) return rc;   // AUTO: what JOINT cannot hold goes to LAZY
+        ss = spg_select_stats{};
+        ss.endpoints = (int32_t)m;
+    }
+    PairBlocks pb;
+    for (int i = 0; i < n; i++) pb.add(ca[i], cb[i], D);
+    DenseStage st;
+    const int staged = cov_stage(g, fixed, order, {&pb.va, &pb.vb}, pb.len(D), nullptr, what, st);
+    if (staged < 0) return staged;
+    const spg::GreedyLazyIn lz{pb.slot.data(), S.data(), (int)m, g->ctx->greedy_lookahead, &g->ctx->greedy_stats};
+    if (int rc = spg::hip_sparse_select(spg::hip_backend_stream(&g->ctx->be), st.in, pb.va.data(), pb.vb.data(), pb.dst.data(), (int32_t)(2 * D),
+                                        (int64_t)pb.va.size(), pb.len(D), ca.data(), cb.data(), sa.data(), sb.data(), n, records, kk, min_gain, max_d2,
+                                        selected, cond_gain, final_gain, status, &nsel, ss, g->ctx->err, sizeof g->ctx->err, &lz)) return rc;
     if (stats) *stats = ss;
     return nsel;
 }
@@ -638,26 +683,47 @@ extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const 
     const int kk = std::min(k, n);
     if (kk == 0) return 0;
     const int64_t m = (int64_t)S.size(), W = m * D, need = W * W;
-    if (W > 46000) {
+    const int method = g->ctx->greedy_method;
+    if (method == SPG_GREEDY_JOINT && W > 46000) {
         snprintf(g->ctx->err, sizeof g->ctx->err, "%s: %lld distinct endpoints, limited to 46k variables, the bound of spg_graph_joint_marginal_covariance",
                  what, (long long)m);
         return SPG_ECAPACITY;
     }
     if (!pruned || !cond_loss || !kld || cap < kk) return kk;
-    std::vector<int32_t> va, vb;
-    std::vector<int64_t> dst;
-    va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
-    for (int64_t a = 0; a < m; a++)
-        for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
-    DenseStage st;
     spg_prune_stats ps{};
     ps.endpoints = (int32_t)m;
-    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
-    if (staged < 0) return staged;
     int npruned = 0;
-    if (int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
-                                       edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, min_margin > 0.0 ? min_margin : 1e-6, pruned, cond_loss,
-                                       kld, final_loss, final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err)) return rc;
+    const double margin = min_margin > 0.0 ? min_margin : 1e-6;
+    if (method == SPG_GREEDY_JOINT || (method == SPG_GREEDY_AUTO && W <= 46000)) {
+        std::vector<int32_t> va, vb;
+        std::vector<int64_t> dst;
+        va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
+        for (int64_t a = 0; a < m; a++)
+            for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
+        DenseStage st;
+        const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
+        if (staged < 0) return staged;
+        const int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
+                                             edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, margin, pruned, cond_loss, kld, final_loss,
+                                             final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err);
+        if (rc == 0) {
+            joint_greedy_stats(g->ctx, ps.rounds);
+            if (stats) *stats = ps;
+            return npruned;
+        }
+        if (!(method == SPG_GREEDY_AUTO && rc == SPG_ECAPACITY)) return rc;   // AUTO: what JOINT cannot hold goes to LAZY
+        ps = spg_prune_stats{};
+        ps.endpoints = (int32_t)m;
+    }
+    PairBlocks pb;   // every pair is an edge: its block lies in the fronts of the selected inverse
+    for (int i = 0; i < n; i++) { const GEdge &ge = g->edges[live[edge_idx[i]]]; pb.add(ge.vtx[0], ge.vtx[1], D); }
+    DenseStage st;
+    const int staged = cov_stage(g, fixed, order, {&pb.va, &pb.vb}, pb.len(D), nullptr, what, st);
+    if (staged < 0) return staged;
+    const spg::GreedyLazyIn lz{pb.slot.data(), S.data(), (int)m, g->ctx->greedy_lookahead, &g->ctx->greedy_stats};
+    if (int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, pb.va.data(), pb.vb.data(), pb.dst.data(), (int32_t)(2 * D),
+                                       (int64_t)pb.va.size(), pb.len(D), edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, margin, pruned, cond_loss,
+                                       kld, final_loss, final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err, &lz)) return rc;
     if (stats) *stats = ps;
     return npruned;
 }

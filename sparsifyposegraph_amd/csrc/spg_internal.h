@@ -131,17 +131,27 @@ int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va,
 // for the m D x m D joint covariance of the candidates' distinct non-fixed endpoints (joint_len doubles, row stride ld, kept
 // on the device); candidate i has the poses of vertex indices ca[i], cb[i] and the endpoint slots sa[i], sb[i] in that
 // block (-1 = the fixed vertex). n, kk >= 1. selected, cond_gain: kk entries; final_gain, status: n each, may be nullptr.
+// lazy != nullptr (SPG_GREEDY_LAZY): no joint block. The sub-block lists then describe one 2D x 2D block per
+// distinct ordered endpoint pair as for hip_sparse_relative (joint_len = their doubles, ld = 2D), pslot[i] is candidate
+// i's block, S the m endpoint vertex indices in slot order, and every round solves the columns of Sigma it reads.
+struct GreedyLazyIn {
+    const int32_t *pslot;     // n
+    const int32_t *S;         // m vertex indices
+    int m;
+    int lookahead;            // as spg_ctx_set_greedy_method takes it
+    spg_greedy_stats *stats;  // rounds, columns, hits, batches, sweep seconds, refactorised, cache bytes
+};
 int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                       int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
                       double min_gain, double max_d2, int32_t *selected, double *cond_gain, double *final_gain, int32_t *status, int *nsel,
-                      spg_select_stats &stats, char *err, size_t errlen);
+                      spg_select_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy = nullptr);
 // Greedy edge pruning (spg_sparse.inc: sp_prune_*_kernel). The sub-block lists and the slots sa / sb as hip_sparse_select;
 // candidate i is live edge eidx[i] of `in` (a binary edge: its record is read from the device arena). n, kk >= 1. pruned,
 // cond_loss, kld: kk entries; final_loss, final_margin, status: n each, may be nullptr.
 int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                      int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
                      double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
-                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen);
+                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy = nullptr);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -28,6 +28,7 @@
 #include <memory>
 #include <queue>
 #include <unordered_map>
+#include "spg_greedy_plan.hpp"
 
 #include "spg_sparse_plan.hpp"
 
@@ -1354,6 +1355,444 @@ __global__ __launch_bounds__(256) void sp_prune_gather_kernel(PruneArgs a) {
     a.status[i] = st != 0 ? st : kept ? 0 : 2;
 }
 
+// ---- lazy forms of the selection and pruning kernels (SPG_GREEDY_LAZY, DESIGN 5g-L): no joint block. Round 0 reads the
+// candidate's own 2D x 2D pair block (pslot, the blocks of sp_relative_kernel); a round reads the four blocks
+// Sigma(a_i | b_i, a* | b*) from the two cache strips of the chosen candidate's endpoints. A strip is Sigma[S, v]: m D x D,
+// row-major, strip_len = m D^2 doubles, rows in the order of the endpoint slots sa / sb. Everything after the load is the
+// text of the joint kernels above, which keep theirs (see the note at rel_geometry): a change to one has to be made in
+// the other. ctl[0..2] as above; rank[0] = i* of the round, rank[1..L) = the next-best eligible candidates in the order
+// of the argmax / argmin (-1: none), the endpoints the host may solve ahead.
+struct LazyArgs {
+    const double *blocks;     // per pair slot (2D)^2, row-major
+    const int32_t *pslot;     // per candidate: its pair block
+    const double *cache;      // the strips
+    long long strip_len;
+    int32_t *rank;            // L entries
+    int L;
+    int ca, cb;               // round kernels: the strips of a*, b* (-1: the fixed vertex)
+};
+// the 2D x 2D block [[S(ra, a*), S(ra, b*)], [S(rb, a*), S(rb, b*)]] out of the strips ca, cb into LDS
+template <int D>
+__device__ __forceinline__ void lazy_load_sigma(int lane, const double *cache, long long strip_len, int ra, int rb, int ca, int cb, double *S) {
+    constexpr int W = 2 * D;
+    for (int k = lane; k < W * W; k += 64) {
+        const int r = k / W, c = k - r * W;
+        const int br = r < D ? ra : rb, bc = c < D ? ca : cb;
+        const int rr = r < D ? r : r - D, cc = c < D ? c : c - D;
+        S[k] = (br < 0 || bc < 0) ? 0.0 : cache[(long long)bc * strip_len + ((long long)br * D + rr) * D + cc];
+    }
+}
+// cache[strip[c]][(j D + r) D + cc] = ws[srow[j] + r R + D c + cc]: the solved panel rows of every endpoint vertex j
+// (srow: where its first row starts in the panel workspace) into the strips of the panel's ncol column vertices.
+// One thread per element, the D ncol panel columns fastest; every strip element has one writer.
+__global__ __launch_bounds__(256) void sp_strip_rows_kernel(const double *ws, const int64_t *srow, int m, int D, int R, const int32_t *strip, int ncol,
+                                                             long long strip_len, double *cache) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)D * ncol;
+    if (idx >= (long long)m * D * per) return;
+    const long long row = idx / per;
+    const int e = (int)(idx - row * per), c = e / D, cc = e - c * D;
+    const int j = (int)(row / D), r = (int)(row - (long long)j * D);
+    cache[(long long)strip[c] * strip_len + row * D + cc] = ws[srow[j] + (long long)r * R + e];
+}
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_init_lazy_kernel(SelArgs a, LazyArgs z) {
+    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3, TRI = D * (D + 1) / 2, REC = PS + TRI;
+    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n;
+    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
+    double *A = T, *M = T + DD;
+    const double *rec = act ? a.rec + (long long)i * REC : nullptr;
+    if (act) {
+        const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
+        for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
+        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.va[i], a.vb[i], rec, nullptr, Ja, Jb, e);
+    }
+    __syncthreads();
+    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
+    __syncthreads();
+    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
+    if (act && lane == 0) {
+        double chi;
+        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
+    }
+    __syncthreads();
+    const bool go = act && okv[w];
+    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
+    __syncthreads();
+    if (go && lane < DD) rel_M<D>(lane, L, A, M);
+    __syncthreads();
+    if (act && lane == 0) {
+        double gain = __builtin_nan(""), d2 = gain;
+        int st = 1;
+        if (go) {
+            rel_chol_M<D>(M, y, gain, d2);
+            st = (a.max_d2 > 0.0 && !(d2 <= a.max_d2)) ? 2 : 0;
+        }
+        a.gain[i] = gain;
+        a.d2[i] = d2;
+        a.state[i] = st;
+    }
+    if (act && lane < DD) {
+        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
+        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
+        a.L[(long long)i * DD + lane] = L[lane];
+        a.C[(long long)i * DD + lane] = P[lane];
+    }
+}
+// Stage 2 of the argmax, lazy form (one workgroup, after stage 1 of sp_select_argmax_kernel): the same choice and the same
+// bookkeeping, then L - 1 passes over the candidates in state 0, each taking the best one that comes after the previous
+// in the order of sel_better: no atomics, independent of the grid of stage 1.
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_rank_kernel(SelArgs a, LazyArgs z) {
+    constexpr int DD = D * D;
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    __shared__ int chosen;
+    const int stop = a.ctl[1];
+    double g = -__builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop)
+        for (int p = threadIdx.x; p < a.np; p += 256)
+            if (sel_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+    sel_reduce(g, bi, sg, si);
+    if (stop) return;
+    if (threadIdx.x == 0) {
+        if (bi == 0x7fffffff || g < a.min_gain) {
+            a.ctl[1] = 1;
+            chosen = -1;
+        } else {
+            const int c = a.ctl[0];
+            a.sel[c] = bi;
+            a.cg[c] = g;
+            a.ctl[0] = c + 1;
+            a.ctl[2] = bi;
+            a.state[bi] = 3;
+            chosen = bi;
+        }
+        z.rank[0] = chosen;
+    }
+    __syncthreads();
+    const int ch = chosen;
+    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
+    double pg = g;
+    int pi = ch >= 0 ? bi : 0x7fffffff;
+    for (int r = 1; r < z.L; r++) {
+        double ng = -__builtin_inf();
+        int ni = 0x7fffffff;
+        if (pi != 0x7fffffff)
+            for (int i = threadIdx.x; i < a.n; i += 256) {
+                if (a.state[i] != 0) continue;
+                const double gi = a.gain[i];
+                if (sel_better(pg, pi, gi, i) && sel_better(gi, i, ng, ni)) { ng = gi; ni = i; }
+            }
+        __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
+        sel_reduce(ng, ni, sg, si);
+        if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
+        pg = ng; pi = ni;
+    }
+}
+template <int D>
+__global__ __launch_bounds__(256) void sp_select_round_lazy_kernel(SelArgs a, LazyArgs z) {
+    constexpr int W = 2 * D, DD = D * D;
+    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
+    __shared__ double lds[4 * PER];
+    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
+    const int s = a.ctl[2], t = a.ctl[0] - 1;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
+    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
+           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD, *y = Ci + DD;
+    if (act) {
+        lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
+        for (int k = lane; k < 2 * DD; k += 64) {
+            Ji[k] = a.J[(long long)i * 2 * DD + k];
+            Js[k] = a.J[(long long)s * 2 * DD + k];
+        }
+        if (lane < DD) {
+            Ls[lane] = a.L[(long long)s * DD + lane];
+            Ms[lane] = a.pubC[lane];
+            Li[lane] = a.L[(long long)i * DD + lane];
+            Ci[lane] = a.C[(long long)i * DD + lane];
+        }
+        if (lane < D) y[lane] = 0.0;
+    }
+    __syncthreads();
+    if (act) {
+        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
+        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        rel_M<D>(lane, Ls, As, Ms);                    // M = I + L*^T C** L*
+        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
+        double x = 0;
+        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
+        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
+        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
+        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
+            x -= d;
+        }
+        X[lane] = x;
+    }
+    __syncthreads();
+    if (act && lane == 0) {
+        double g, d2;
+        rel_chol_M<D>(Ms, y, g, d2);                   // G in the lower triangle of Ms
+    }
+    __syncthreads();
+    if (act && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
+        const int r = lane;
+        for (int j = 0; j < D; j++) {
+            double v = (j <= r) ? Ls[r * D + j] : 0.0;
+            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
+            K[r * D + j] = v / Ms[j * D + j];
+        }
+    }
+    __syncthreads();
+    if (act && lane < DD) {                            // B_i,t = X K, appended to the history
+        const int r = lane / D, c = lane - r * D;
+        double v = 0;
+        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
+        B[lane] = v;
+        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
+    }
+    __syncthreads();
+    if (act && lane < DD) {                            // C_ii -= B B^T, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
+            const double v = Ci[r * D + c] - d;
+            Ci[r * D + c] = v;
+            Ci[c * D + r] = v;
+        }
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        a.C[(long long)i * DD + lane] = Ci[lane];
+        if (go) rel_PL<D>(lane, Ci, Li, As);
+    }
+    __syncthreads();
+    if (go && lane < DD) rel_M<D>(lane, Li, As, Ms);
+    __syncthreads();
+    if (go && lane == 0) {
+        double g, d2;
+        rel_chol_M<D>(Ms, y, g, d2);
+        a.gain[i] = g;
+    }
+}
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_init_lazy_kernel(PruneArgs a, LazyArgs z) {
+    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3;
+    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n;
+    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
+    double *A = T, *M = T + DD;
+    const spg_edge_ref *er = act ? a.er + a.eidx[i] : nullptr;
+    const double *rec = act ? a.arena + er->off : nullptr;
+    if (act) {
+        const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
+        for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
+        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.ev[er->vbegin], a.ev[er->vbegin + 1], rec, nullptr, Ja, Jb, e);
+    }
+    __syncthreads();
+    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
+    __syncthreads();
+    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
+    if (act && lane == 0) {
+        double chi;
+        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
+    }
+    __syncthreads();
+    const bool go = act && okv[w];
+    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
+    __syncthreads();
+    if (go && lane == 0) {           // tr(L^T P L) before M takes A's neighbour
+        double tr = 0;
+        for (int c = 0; c < D; c++)
+            for (int t = c; t < D; t++) tr += L[t * D + c] * A[t * D + c];
+        a.tr0[i] = tr;
+    }
+    if (go && lane < DD) rel_M_down<D>(lane, L, A, M);
+    __syncthreads();
+    if (act && lane == 0) {
+        double loss = __builtin_nan(""), margin = loss;
+        if (go) rel_chol_downdate<D>(M, a.min_margin, loss, margin);
+        else a.tr0[i] = loss;
+        a.loss[i] = loss;
+        a.margin[i] = margin;
+        a.state[i] = go ? 0 : 1;
+    }
+    if (act && lane < DD) {
+        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
+        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
+        a.L[(long long)i * DD + lane] = L[lane];
+        a.C[(long long)i * DD + lane] = P[lane];
+    }
+}
+// Stage 2 of the argmin, lazy form: the choice, stop rules and bookkeeping of sp_prune_argmin_kernel(pick = 1), then the
+// ranked list over the candidates eligible this round, in the order of prn_better.
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_rank_kernel(PruneArgs a, LazyArgs z) {
+    constexpr int DD = D * D;
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    __shared__ int chosen;
+    const int stop = a.ctl[1];
+    double g = __builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop)
+        for (int p = threadIdx.x; p < a.np; p += 256)
+            if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+    prn_reduce(g, bi, sg, si);
+    if (stop) return;
+    if (threadIdx.x == 0) {
+        chosen = -1;
+        if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
+            a.ctl[1] = 1;
+        } else {
+            const double kld = a.kldsum[0] + (g - 0.5 * a.tr0[bi]);
+            if (a.max_kld > 0.0 && kld > a.max_kld) {
+                a.ctl[1] = 1;
+            } else {
+                const int c = a.ctl[0];
+                a.sel[c] = bi;
+                a.cl[c] = g;
+                a.ck[c] = kld;
+                a.kldsum[0] = kld;
+                a.ctl[0] = c + 1;
+                a.ctl[2] = bi;
+                a.state[bi] = 3;
+                chosen = bi;
+            }
+        }
+        z.rank[0] = chosen;
+    }
+    __syncthreads();
+    const int ch = chosen;
+    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
+    double pg = g;
+    int pi = ch >= 0 ? bi : 0x7fffffff;
+    for (int r = 1; r < z.L; r++) {
+        double ng = __builtin_inf();
+        int ni = 0x7fffffff;
+        if (pi != 0x7fffffff)
+            for (int i = threadIdx.x; i < a.n; i += 256) {
+                const double l = a.loss[i];
+                if (a.state[i] != 0 || !(l == l) || !(a.margin[i] >= a.min_margin)) continue;
+                if (prn_better(pg, pi, l, i) && prn_better(l, i, ng, ni)) { ng = l; ni = i; }
+            }
+        __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
+        prn_reduce(ng, ni, sg, si);
+        if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
+        pg = ng; pi = ni;
+    }
+}
+template <int D>
+__global__ __launch_bounds__(256) void sp_prune_round_lazy_kernel(PruneArgs a, LazyArgs z) {
+    constexpr int W = 2 * D, DD = D * D;
+    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
+    __shared__ double lds[4 * PER];
+    __shared__ int okv[4];
+    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
+    const int s = a.ctl[2], t = a.ctl[0] - 1;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
+    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
+    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
+           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD;
+    if (act) {
+        lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
+        for (int k = lane; k < 2 * DD; k += 64) {
+            Ji[k] = a.J[(long long)i * 2 * DD + k];
+            Js[k] = a.J[(long long)s * 2 * DD + k];
+        }
+        if (lane < DD) {
+            Ls[lane] = a.L[(long long)s * DD + lane];
+            Ms[lane] = a.pubC[lane];
+            Li[lane] = a.L[(long long)i * DD + lane];
+            Ci[lane] = a.C[(long long)i * DD + lane];
+        }
+    }
+    __syncthreads();
+    if (act) {
+        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
+        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
+    }
+    __syncthreads();
+    if (act && lane < DD) {
+        rel_M_down<D>(lane, Ls, As, Ms);               // M = I - L*^T C** L*
+        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
+        double x = 0;
+        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
+        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
+        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
+        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
+            x += d;
+        }
+        X[lane] = x;
+    }
+    __syncthreads();
+    if (act && lane == 0) {
+        double l, m;
+        okv[w] = rel_chol_downdate<D>(Ms, 0.0, l, m);  // G in the lower triangle of Ms
+        if (!okv[w]) { a.loss[i] = __builtin_nan(""); a.margin[i] = __builtin_nan(""); }
+    }
+    __syncthreads();
+    const bool upd = act && okv[w];
+    if (upd && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
+        const int r = lane;
+        for (int j = 0; j < D; j++) {
+            double v = (j <= r) ? Ls[r * D + j] : 0.0;
+            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
+            K[r * D + j] = v / Ms[j * D + j];
+        }
+    }
+    __syncthreads();
+    if (upd && lane < DD) {                            // B_i,t = X K, appended to the history
+        const int r = lane / D, c = lane - r * D;
+        double v = 0;
+        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
+        B[lane] = v;
+        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
+    }
+    __syncthreads();
+    if (upd && lane < DD) {                            // C_ii += B B^T, r <= c, mirrored
+        const int r = lane / D, c = lane - r * D;
+        if (r <= c) {
+            double d = 0;
+            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
+            const double v = Ci[r * D + c] + d;
+            Ci[r * D + c] = v;
+            Ci[c * D + r] = v;
+        }
+    }
+    __syncthreads();
+    const bool re = upd && go;
+    if (upd && lane < DD) {
+        a.C[(long long)i * DD + lane] = Ci[lane];
+        if (go) rel_PL<D>(lane, Ci, Li, As);
+    }
+    __syncthreads();
+    if (re && lane < DD) rel_M_down<D>(lane, Li, As, Ms);
+    __syncthreads();
+    if (re && lane == 0) {
+        double l, m;
+        rel_chol_downdate<D>(Ms, a.min_margin, l, m);
+        a.loss[i] = l;
+        a.margin[i] = m;
+    }
+}
+
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
 // (src/utils.cpp:70-97) = 0.5 (tr(Sx^-1 Sy) + diff^T Sx^-1 diff + log det Sx - log det Sy - D), through the Cholesky
 // factors Sx = Lx Lx^T, Sy = Ly Ly^T: tr = || Lx^-1 Ly ||_F^2, Mahalanobis = || Lx^-1 diff ||^2. One lane per vertex,
@@ -1901,6 +2340,7 @@ struct ColumnSolves {
     int per_batch = 1, nbatch = 0;
     double flops = 0, seconds = 0;
     std::vector<int32_t> fw, bw, stamp_list;
+    std::vector<int32_t> bw_always;   // supernodes every batch sweeps backward over (the lazy greedy rounds: the paths of all of S)
     int32_t stamp = 0;
     std::vector<int64_t> off;
     ColumnSolves(SparseSolver &s_, const std::vector<int32_t> &row, const std::vector<int32_t> &col) : sp(s_), P(s_.plan), D(s_.D) {
@@ -1935,6 +2375,7 @@ struct ColumnSolves {
             up(fw, cols[c]);
             for (int32_t k = rq_ptr[c]; k < rq_ptr[c + 1]; k++) up(bw, rq_row[k]);
         }
+        for (int32_t s : bw_always) bw[s] = stamp;
         const int R = width(b);
         int64_t len = 0;
         for (int s : P.level_sn)
@@ -2098,62 +2539,150 @@ struct ColumnSolves {
         }
         EventTimer timer;   // one batch at a time
         float ms = 0;
-        for (int b = 0; b < nbatch; b++) {
-            build(b, (double *)ws.p);
-            // one upload per batch: gemm items | panel pairs | seeds | cross sources | cross destinations
-            const size_t o_pp = gi.size() * sizeof(GemmItem), o_sd = o_pp + pp.size() * sizeof(PanelPair), o_cs = o_sd + seeds.size() * 8,
-                         o_cd = o_cs + csrc.size() * 8, nbytes = o_cd + cdst.size() * 4;
-            hb.resize(nbytes);
-            memcpy(hb.data(), gi.data(), o_pp);
-            memcpy(hb.data() + o_pp, pp.data(), o_sd - o_pp);
-            memcpy(hb.data() + o_sd, seeds.data(), o_cs - o_sd);
-            memcpy(hb.data() + o_cs, csrc.data(), o_cd - o_cs);
-            memcpy(hb.data() + o_cd, cdst.data(), nbytes - o_cd);
-            if (b > 0) {   // the previous batch still reads the blob and the panels
-                COLCHK("a batch", hipStreamSynchronize(s));
-                COLCHK("hipEventElapsedTime", timer.ms(ms));
-                seconds += 1e-3 * ms;
-            }
-            if (nbytes > blob_cap) {
-                if (blob.p) { (void)hipFree(blob.p); blob.p = nullptr; }
-                blob_cap = nbytes + nbytes / 4;
-                COLCHK("hipMalloc of the item lists", hipMalloc(&blob.p, blob_cap));
-            }
-            COLCHK("uploading the item lists", hipMemcpy(blob.p, hb.data(), nbytes, hipMemcpyHostToDevice));
-            const char *B = (const char *)blob.p;
-            const int R = width(b);
-            int64_t len = 0;
-            for (int sn : P.level_sn) if (fw[sn] == stamp || bw[sn] == stamp) len += (int64_t)P.ld(sn) * R;
-            COLCHK(timer.made != hipSuccess ? "hipEventCreate" : "hipEventRecord", timer.start(s));
-            COLCHK("hipMemsetAsync", hipMemsetAsync(ws.p, 0, (size_t)std::max<int64_t>(len, 1) * 8, s));
-            for (const Step &st : steps) {
-                const PanelPair *pairs = (const PanelPair *)(B + o_pp) + st.begin;
-                switch (st.kind) {
-                case GEMM:
-                    hipLaunchKernelGGL(sp_gemm_items_kernel, dim3(st.count), dim3(256), 0, s, (const GemmItem *)B + st.begin);
-                    break;
-                case EXTADD:
-                    by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
-                    break;
-                case GATHER:
-                    by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
-                    break;
-                case SEED:
-                    hipLaunchKernelGGL(sp_panel_seed_kernel, dim3((st.count + 255) / 256), dim3(256), 0, s, (double *)ws.p, (const int64_t *)(B + o_sd), st.count);
-                    break;
-                case CROSS:
-                    if (st.count > 0)
-                        hipLaunchKernelGGL(sp_cross_rows_kernel, dim3((st.count * D * D + 255) / 256), dim3(256), 0, s, (const double *)ws.p, (const int64_t *)(B + o_cs),
-                                           (const int32_t *)(B + o_cd), st.count, D, R, cross);
-                    break;
-                }
-            }
-            COLCHK("a launch", hipGetLastError());
-            COLCHK("hipEventRecord", timer.stop(s));
-        }
+        for (int b = 0; b < nbatch; b++)
+            if (int rc = enqueue(s, b, ws, blob, blob_cap, hb, timer, b > 0, cross, err, errlen)) return rc;
         COLCHK("a batch", hipStreamSynchronize(s));
         COLCHK("hipEventElapsedTime", timer.ms(ms));
         seconds += 1e-3 * ms;
+        return 0;
+    }
+    // Batch b into the stream, inside the timer's event pair: item lists built and uploaded (the blob grows as needed), the
+    // panels of ws zeroed and seeded, forward, backward, the requested rows -> cross. wait_prev: the stream still runs a
+    // batch that reads the blob and the panels; it is waited for and its time is added to `seconds` first.
+    int enqueue(hipStream_t s, int b, DevBuf &ws, DevBuf &blob, size_t &blob_cap, std::vector<char> &hb, EventTimer &timer, bool wait_prev, double *cross,
+                char *err, size_t errlen) {
+        build(b, (double *)ws.p);
+        // one upload per batch: gemm items | panel pairs | seeds | cross sources | cross destinations
+        const size_t o_pp = gi.size() * sizeof(GemmItem), o_sd = o_pp + pp.size() * sizeof(PanelPair), o_cs = o_sd + seeds.size() * 8,
+                     o_cd = o_cs + csrc.size() * 8, nbytes = o_cd + cdst.size() * 4;
+        hb.resize(nbytes);
+        memcpy(hb.data(), gi.data(), o_pp);
+        memcpy(hb.data() + o_pp, pp.data(), o_sd - o_pp);
+        memcpy(hb.data() + o_sd, seeds.data(), o_cs - o_sd);
+        memcpy(hb.data() + o_cs, csrc.data(), o_cd - o_cs);
+        memcpy(hb.data() + o_cd, cdst.data(), nbytes - o_cd);
+        if (wait_prev) {
+            float ms = 0;
+            COLCHK("a batch", hipStreamSynchronize(s));
+            COLCHK("hipEventElapsedTime", timer.ms(ms));
+            seconds += 1e-3 * ms;
+        }
+        if (nbytes > blob_cap) {
+            if (blob.p) { (void)hipFree(blob.p); blob.p = nullptr; }
+            blob_cap = nbytes + nbytes / 4;
+            COLCHK("hipMalloc of the item lists", hipMalloc(&blob.p, blob_cap));
+        }
+        COLCHK("uploading the item lists", hipMemcpy(blob.p, hb.data(), nbytes, hipMemcpyHostToDevice));
+        const char *B = (const char *)blob.p;
+        const int R = width(b);
+        int64_t len = 0;
+        for (int sn : P.level_sn) if (fw[sn] == stamp || bw[sn] == stamp) len += (int64_t)P.ld(sn) * R;
+        COLCHK(timer.made != hipSuccess ? "hipEventCreate" : "hipEventRecord", timer.start(s));
+        COLCHK("hipMemsetAsync", hipMemsetAsync(ws.p, 0, (size_t)std::max<int64_t>(len, 1) * 8, s));
+        for (const Step &st : steps) {
+            const PanelPair *pairs = (const PanelPair *)(B + o_pp) + st.begin;
+            switch (st.kind) {
+            case GEMM:
+                hipLaunchKernelGGL(sp_gemm_items_kernel, dim3(st.count), dim3(256), 0, s, (const GemmItem *)B + st.begin);
+                break;
+            case EXTADD:
+                by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, false>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
+                break;
+            case GATHER:
+                by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_panel_rows_kernel<decltype(d)::value, true>), dim3(st.count, st.gy, st.gz), dim3(256), 0, s, pairs); });
+                break;
+            case SEED:
+                hipLaunchKernelGGL(sp_panel_seed_kernel, dim3((st.count + 255) / 256), dim3(256), 0, s, (double *)ws.p, (const int64_t *)(B + o_sd), st.count);
+                break;
+            case CROSS:
+                if (st.count > 0)
+                    hipLaunchKernelGGL(sp_cross_rows_kernel, dim3((st.count * D * D + 255) / 256), dim3(256), 0, s, (const double *)ws.p, (const int64_t *)(B + o_cs),
+                                       (const int32_t *)(B + o_cd), st.count, D, R, cross);
+                break;
+            }
+        }
+        COLCHK("a launch", hipGetLastError());
+        COLCHK("hipEventRecord", timer.stop(s));
+        return 0;
+    }
+};
+
+// The per-round column solves of the lazy greedy calls (DESIGN 5g-L) and the column cache they fill. One 64-wide panel
+// per round: forward over the root paths of the new column vertices, backward over the paths of all of S — the same set
+// every round, marked once (bw_always), so the panel layout, the workspace and the rows the strips are read from are fixed
+// for the call. SPG_GREEDY_CACHE_STRIPS=<n> (diagnostic) caps the cache at n >= 2 strips.
+struct LazySweeps {
+    static const std::vector<int32_t> &none() { static const std::vector<int32_t> v; return v; }
+    ColumnSolves cs;
+    const int D, m;
+    std::vector<int32_t> q;          // per endpoint slot: block position
+    DevBuf ws, blob, dsrow, dstrip, cache;
+    size_t blob_cap = 0;
+    std::vector<char> hb;
+    EventTimer timer;
+    bool pending = false;            // a panel is in the stream whose time has not been read
+    long long strip_len = 0;
+    int nstrips = 0, batches = 0;
+    LazySweeps(SparseSolver &sp, std::vector<int32_t> q_) : cs(sp, none(), none()), D(sp.D), m((int)q_.size()), q(std::move(q_)) {}
+    // reserved: bytes the caller has yet to allocate. The cache takes what is left of free HBM (1 GB kept free), at most m
+    // strips and at most max_strips, what the rounds of the call can fill.
+    int init(double reserved, long long max_strips, char *err, size_t errlen) {
+        const Plan &P = cs.P;
+        std::vector<uint8_t> mk((size_t)P.nsn, 0);
+        for (int32_t v : q)
+            for (int sn = P.sn_of[v]; sn >= 0 && !mk[sn]; sn = P.parent[sn]) { mk[sn] = 1; cs.bw_always.push_back(sn); }
+        cs.per_batch = spg::kGreedyPanel / D;
+        cs.nbatch = 1;
+        cs.cols.assign(1, q[0]);
+        cs.rq_ptr.assign(2, 0);
+        const int64_t ws_len = cs.touch(0);
+        strip_len = (long long)m * D * D;
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        const double avail = (double)free_b - (double)(1ull << 30) - reserved - (double)ws_len * 8 - 64.0e6;
+        long long fit = avail <= 0 ? 0 : (long long)(avail / ((double)strip_len * 8));
+        if (const char *e = getenv("SPG_GREEDY_CACHE_STRIPS")) { const int v = atoi(e); if (v > 0) fit = std::min<long long>(fit, std::max(2, v)); }
+        if (fit < 2) {
+            snprintf(err, errlen, "lazy greedy rounds need a %.2f GB panel workspace and two %.2f GB column strips, %.2f GB of HBM are free",
+                     ws_len * 8e-9, strip_len * 8e-9, free_b * 1e-9);
+            return SPG_ECAPACITY;
+        }
+        nstrips = (int)std::min<long long>(fit, std::max<long long>(2, std::min<long long>(m, max_strips)));
+        COLCHK("hipMalloc of the panel workspace", hipMalloc(&ws.p, (size_t)std::max<int64_t>(ws_len, 1) * 8));
+        COLCHK("hipMalloc of the column cache", hipMalloc(&cache.p, (size_t)nstrips * strip_len * 8));
+        COLCHK("hipMalloc", hipMalloc(&dstrip.p, spg::kGreedyPanel * sizeof(int32_t)));
+        std::vector<int64_t> srow((size_t)m);
+        for (int j = 0; j < m; j++) { const int sn = P.sn_of[q[j]]; srow[j] = cs.off[sn] + (int64_t)D * (q[j] - P.first[sn]) * spg::kGreedyPanel; }
+        COLCHK("hipMalloc", hipMalloc(&dsrow.p, (size_t)m * 8));
+        COLCHK("uploading the strip rows", hipMemcpy(dsrow.p, srow.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+        return 0;
+    }
+    double cache_bytes() const { return (double)nstrips * strip_len * 8; }
+    // after a synchronisation of the stream: the time of the panel in flight
+    int collect(char *err, size_t errlen) {
+        if (!pending) return 0;
+        float ms = 0;
+        COLCHK("hipEventElapsedTime", timer.ms(ms));
+        cs.seconds += 1e-3 * ms;
+        pending = false;
+        return 0;
+    }
+    // The columns of gr.solve_vertex into the strips gr.solve_strip. The stream is idle: the caller has read the round's
+    // control words.
+    int solve(hipStream_t s, const spg::GreedyRound &gr, char *err, size_t errlen) {
+        const int nc = (int)gr.solve_vertex.size();
+        if (nc == 0) return 0;
+        cs.cols.resize((size_t)nc);
+        for (int c = 0; c < nc; c++) cs.cols[c] = q[gr.solve_vertex[c]];
+        cs.rq_ptr.assign((size_t)nc + 1, 0);
+        COLCHK("uploading the strip slots", hipMemcpy(dstrip.p, gr.solve_strip.data(), (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (int rc = cs.enqueue(s, 0, ws, blob, blob_cap, hb, timer, false, nullptr, err, errlen)) return rc;
+        pending = true;
+        batches++;
+        const long long total = (long long)m * D * D * nc;
+        hipLaunchKernelGGL(sp_strip_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const double *)ws.p, (const int64_t *)dsrow.p, m, D,
+                           spg::kGreedyPanel, (const int32_t *)dstrip.p, nc, strip_len, (double *)cache.p);
+        COLCHK("a launch", hipGetLastError());
         return 0;
     }
 };
@@ -2383,9 +2912,14 @@ int hip_sparse_cov_blocks(void *stream, const DenseGraphIn &in, int K, const int
 // cov_solve_device leaves the assembled sub-blocks in dout (device, out_len doubles); `tail`, if given, launches what
 // consumes them there (it sees the staged graph; its launches are inside the selected inverse's event pair) before the
 // fronts are released. hip_sparse_cov_solve adds the copy to the host.
+// `post`, if given, runs last, after the synchronisation and the checks, while the solver and the staged graph are
+// still alive (the lazy greedy rounds): it gets the solver, whose fronts then hold the selected inverse, the staged graph,
+// the device flags and pos (per vertex index: D * elimination position).
 using CovTail = std::function<void(hipStream_t, const GraphBufs &, const double *)>;
+using CovPost = std::function<int(hipStream_t, SparseSolver &, const GraphBufs &, int *, const std::vector<int32_t> &)>;
 static int cov_solve_device(hipStream_t s, const DenseGraphIn &in_, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
-                            int64_t out_len, DevBuf &dout, spg_cov_solve_stats &stats, char *err, size_t errlen, const CovTail *tail) {
+                            int64_t out_len, DevBuf &dout, spg_cov_solve_stats &stats, char *err, size_t errlen, const CovTail *tail,
+                            const CovPost *post = nullptr) {
     const int D = in_.D;
     const bool force = cov_force_solve();
     int rc = 0;
@@ -2465,6 +2999,7 @@ static int cov_solve_device(hipStream_t s, const DenseGraphIn &in_, const int32_
     sp->count_into(stats.cov);
     stats.cov.device_seconds += 1e-3 * (ms0 + ms1) + cs.seconds;
     stats.columns += (int32_t)cs.cols.size(); stats.rhs_batches += cs.nbatch; stats.solve_flops += cs.flops; stats.solve_seconds += cs.seconds;
+    if (post) return (*post)(s, *sp, gb, (int *)bad.p, pos);
     return 0;
 }
 
@@ -2521,6 +3056,80 @@ int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va,
     return 0;
 }
 
+// ---- the lazy mode of the two greedy calls (SPG_GREEDY_LAZY, DESIGN 5g-L)
+constexpr int kGreedyCtl = 4 + 16;   // control words, then the ranked list (at most 64 / 2D = 10 candidates)
+
+// the free-HBM check of a lazy call, before anything is allocated; the panel workspace is checked once the plan is known
+static int greedy_lazy_capacity(const char *what, double own_bytes, int64_t blocks_len, int D, int m, char *err, size_t errlen) {
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double strips = 2.0 * 8.0 * (double)m * D * D;
+    if (own_bytes + strips + (double)(1ull << 30) <= (double)free_b) return 0;
+    snprintf(err, errlen, "%s (lazy) needs %.2f GB of pair blocks, %.2f GB of histories and state and %.2f GB for two column strips, %.1f GB are free",
+             what, blocks_len * 8e-9, (own_bytes - 8.0 * (double)blocks_len) * 1e-9, strips * 1e-9, free_b * 1e-9);
+    return SPG_ECAPACITY;
+}
+
+// The rounds of a lazy call, after round 0 (init kernel, in the selected inverse's event pair) has been synchronised: the
+// factor is rebuilt (the selected inverse overwrote it), then per round: pick() = argmax / argmin stage 1 and the lazy
+// stage 2; the host reads the control words and the ranked list (one synchronisation), stops on the device's stop word,
+// lets the planner choose the columns to solve, sweeps them into their strips and launches round() with the strips of
+// a*, b* in z. gather() and the call's timer end the device part.
+template <class Pick, class Round, class Gather>
+static int greedy_lazy_rounds(hipStream_t st, SparseSolver &sp, const GraphBufs &gb, int *bad, const std::vector<int32_t> &pos, const GreedyLazyIn &lz, int look,
+                              const int32_t *sa, const int32_t *sb, int kk, int32_t *dctl, LazyArgs &z, EventTimer &t_call, spg_cov_solve_stats &cstats,
+                              char *err, size_t errlen, Pick pick, Round round, Gather gather) {
+    const int D = sp.D;
+    std::vector<int32_t> q((size_t)lz.m);
+    for (int j = 0; j < lz.m; j++) q[j] = pos[lz.S[j]] / D;
+    LazySweeps sw(sp, std::move(q));
+    if (int rc = sw.init(0.0, (long long)kk * (kGreedyPanel / D), err, errlen)) return rc;
+    z.cache = (const double *)sw.cache.p;
+    z.strip_len = sw.strip_len;
+    EventTimer t_post;
+    HIPCHK(t_post.start(st));
+    if (int rc = sp.factorise(st, gb, bad)) { snprintf(err, errlen, "sparse assembly failed"); return rc; }
+    GreedyColumnCache cache(lz.m, sw.nstrips, kGreedyPanel / D, look);
+    GreedyRound gr;
+    int32_t h[kGreedyCtl];
+    int rounds = 0;
+    for (int t = 0; t < kk; t++) {
+        pick();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h, dctl, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (int rc = sw.collect(err, errlen)) return rc;
+        if (h[1]) break;
+        if (h[4] < 0 || h[4] != h[2]) { snprintf(err, errlen, "lazy greedy rounds: the ranked list does not start with the chosen candidate"); return SPG_ESTATE; }
+        cache.plan(h + 4, look, sa, sb, gr);
+        if (int rc = sw.solve(st, gr, err, errlen)) return rc;
+        z.ca = gr.strip_a; z.cb = gr.strip_b;
+        round();
+        rounds++;
+    }
+    gather();
+    HIPCHK(hipGetLastError());
+    HIPCHK(t_call.stop(st));
+    HIPCHK(t_post.stop(st));
+    int h_bad[2] = {0, 0};
+    float ms = 0;
+    HIPCHK(hipMemcpyAsync(h_bad, bad, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = sw.collect(err, errlen)) return rc;
+    if (int rc = cov_bad_flags(h_bad, err, errlen)) return rc;
+    HIPCHK(t_post.ms(ms));
+    cstats.cov.device_seconds += 1e-3 * ms;
+    if (lz.stats) {
+        spg_greedy_stats &gs = *lz.stats;
+        gs = spg_greedy_stats{};
+        gs.method = SPG_GREEDY_LAZY; gs.lookahead = look; gs.rounds = rounds; gs.refactorised = 1;
+        gs.column_vertices = cache.column_vertices; gs.column_hits = cache.column_hits;
+        gs.rhs_batches = sw.batches; gs.evictions = (int32_t)cache.evictions;
+        gs.round_solve_seconds = sw.cs.seconds; gs.cache_bytes = sw.cache_bytes();
+    }
+    return 0;
+}
+
 // spg_graph_select_candidates: the sub-block lists describe the m D x m D joint covariance of the candidates' endpoints
 // (joint_len doubles, row stride ld, kept on the device); candidate i has the poses of vertex indices ca[i], cb[i] and
 // the endpoint slots sa[i], sb[i] (-1: the fixed vertex). The tail enqueues init, kk x (argmax, argmax, round) and the
@@ -2529,12 +3138,16 @@ int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va,
 int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                       int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
                       double min_gain, double max_d2, int32_t *selected, double *cond_gain, double *final_gain, int32_t *status, int *nsel,
-                      spg_select_stats &stats, char *err, size_t errlen) {
+                      spg_select_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
     hipStream_t s = (hipStream_t)stream;
     const int D = in.D, DD = D * D, PS = D == 6 ? 7 : 3, REC = PS + D * (D + 1) / 2;
     const int np = std::min((n + 255) / 256, 256);
+    const int look = lazy ? greedy_lookahead(lazy->lookahead, D) : 0;
+    const double own_bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
     int rc = 0;
-    {
+    if (lazy) {
+        if ((rc = greedy_lazy_capacity("candidate selection", own_bytes, joint_len, D, lazy->m, err, errlen))) return rc;
+    } else {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
@@ -2544,9 +3157,9 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
             return SPG_ECAPACITY;
         }
     }
-    DevBuf djoint, dca, dcb, dsa, dsb, drec, dJ, dL, dC, dhist, dgain, dd2, dstate, dpg, dpi, dctl, dpub, dsel, dcg, dfinal;
+    DevBuf djoint, dca, dcb, dsa, dsb, drec, dJ, dL, dC, dhist, dgain, dd2, dstate, dpg, dpi, dctl, dpub, dsel, dcg, dfinal, dpslot;
     if ((rc = upload(dca, ca, (size_t)n, s)) || (rc = upload(dcb, cb, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) ||
-        (rc = upload(dsb, sb, (size_t)n, s)) || (rc = upload(drec, rec, (size_t)n * REC, s))) {
+        (rc = upload(dsb, sb, (size_t)n, s)) || (rc = upload(drec, rec, (size_t)n * REC, s)) || (lazy && (rc = upload(dpslot, lazy->pslot, (size_t)n, s)))) {
         snprintf(err, errlen, "staging the candidates failed (%d)", rc);
         return rc;
     }
@@ -2559,7 +3172,7 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     HIPCHK(hipMalloc(&dstate.p, (size_t)n * sizeof(int32_t)));
     HIPCHK(hipMalloc(&dpg.p, (size_t)np * 8));
     HIPCHK(hipMalloc(&dpi.p, (size_t)np * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&dctl.p, 4 * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dctl.p, kGreedyCtl * sizeof(int32_t)));   // 4 control words, then the lazy form's ranked list
     HIPCHK(hipMalloc(&dpub.p, (size_t)DD * 8));
     HIPCHK(hipMalloc(&dsel.p, (size_t)kk * sizeof(int32_t)));
     HIPCHK(hipMalloc(&dcg.p, (size_t)kk * 8));
@@ -2569,8 +3182,9 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     HIPCHK(hipMemsetAsync(dcg.p, 0xff, (size_t)kk * 8, s));                  // NaN
     EventTimer t_select;
     hipError_t tail_err = hipSuccess;
+    SelArgs a{};
+    LazyArgs z{};
     const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
-        SelArgs a{};
         a.arena = gb.dev.arena; a.vpo = gb.dev.vpo;
         a.va = (const int32_t *)dca.p; a.vb = (const int32_t *)dcb.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
         a.rec = (const double *)drec.p; a.joint = joint; a.ld = ld;
@@ -2581,6 +3195,12 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
         a.n = n; a.kk = kk; a.np = np; a.min_gain = min_gain; a.max_d2 = max_d2;
         const dim3 per_cand((unsigned)((n + 3) / 4));
         tail_err = t_select.start(st);
+        if (lazy) {   // round 0 from the pair blocks; the rounds follow in `post`, on the factor
+            a.joint = nullptr; a.ld = 0;
+            z.blocks = joint; z.pslot = (const int32_t *)dpslot.p; z.rank = (int32_t *)dctl.p + 4; z.L = look; z.ca = z.cb = -1;
+            by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_select_init_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); });
+            return;
+        }
         by_dim(D, [&](auto d) {
             constexpr int DV = decltype(d)::value;
             hipLaunchKernelGGL((sp_select_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
@@ -2593,7 +3213,19 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
         hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
         if (tail_err == hipSuccess) tail_err = t_select.stop(st);
     };
-    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail))) return rc;
+    const CovPost post = [&](hipStream_t st, SparseSolver &sp, const GraphBufs &gb, int *bad, const std::vector<int32_t> &pos) -> int {
+        const dim3 per_cand((unsigned)((n + 3) / 4));
+        return greedy_lazy_rounds(st, sp, gb, bad, pos, *lazy, look, sa, sb, kk, (int32_t *)dctl.p, z, t_select, stats.solve, err, errlen,
+            [&] {
+                by_dim(D, [&](auto d) {
+                    hipLaunchKernelGGL((sp_select_argmax_kernel<decltype(d)::value>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
+                    hipLaunchKernelGGL((sp_select_rank_kernel<decltype(d)::value>), dim3(1), dim3(256), 0, st, a, z);
+                });
+            },
+            [&] { by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_select_round_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); }); },
+            [&] { hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a); });
+    };
+    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail, lazy ? &post : nullptr))) return rc;
     HIPCHK(tail_err);
     float ms = 0;
     HIPCHK(t_select.ms(ms));
@@ -2616,12 +3248,16 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
 int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                      int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
                      double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
-                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen) {
+                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
     hipStream_t s = (hipStream_t)stream;
     const int D = in.D, DD = D * D;
     const int np = std::min((n + 255) / 256, 256);
+    const int look = lazy ? greedy_lookahead(lazy->lookahead, D) : 0;
+    const double own_bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
     int rc = 0;
-    {
+    if (lazy) {
+        if ((rc = greedy_lazy_capacity("edge pruning", own_bytes, joint_len, D, lazy->m, err, errlen))) return rc;
+    } else {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
@@ -2631,8 +3267,9 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
             return SPG_ECAPACITY;
         }
     }
-    DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus;
-    if ((rc = upload(deidx, eidx, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) || (rc = upload(dsb, sb, (size_t)n, s))) {
+    DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus, dpslot;
+    if ((rc = upload(deidx, eidx, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) || (rc = upload(dsb, sb, (size_t)n, s)) ||
+        (lazy && (rc = upload(dpslot, lazy->pslot, (size_t)n, s)))) {
         snprintf(err, errlen, "staging the candidates failed (%d)", rc);
         return rc;
     }
@@ -2646,7 +3283,7 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     HIPCHK(hipMalloc(&dstate.p, (size_t)n * sizeof(int32_t)));
     HIPCHK(hipMalloc(&dpg.p, (size_t)np * 8));
     HIPCHK(hipMalloc(&dpi.p, (size_t)np * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&dctl.p, 4 * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&dctl.p, kGreedyCtl * sizeof(int32_t)));   // 4 control words, then the lazy form's ranked list
     HIPCHK(hipMalloc(&dpub.p, (size_t)DD * 8));
     HIPCHK(hipMalloc(&dksum.p, 8));
     HIPCHK(hipMalloc(&dsel.p, (size_t)kk * sizeof(int32_t)));
@@ -2662,8 +3299,9 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     HIPCHK(hipMemsetAsync(dck.p, 0xff, (size_t)kk * 8, s));
     EventTimer t_prune;
     hipError_t tail_err = hipSuccess;
+    PruneArgs a{};
+    LazyArgs z{};
     const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
-        PruneArgs a{};
         a.arena = gb.dev.arena; a.vpo = gb.dev.vpo; a.er = gb.dev.er; a.ev = gb.dev.ev;
         a.eidx = (const int32_t *)deidx.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
         a.joint = joint; a.ld = ld;
@@ -2675,6 +3313,12 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
         a.n = n; a.kk = kk; a.np = np; a.max_loss = max_loss; a.max_kld = max_kld; a.min_margin = min_margin;
         const dim3 per_cand((unsigned)((n + 3) / 4));
         tail_err = t_prune.start(st);
+        if (lazy) {   // round 0 from the pair blocks; the rounds follow in `post`, on the factor
+            a.joint = nullptr; a.ld = 0;
+            z.blocks = joint; z.pslot = (const int32_t *)dpslot.p; z.rank = (int32_t *)dctl.p + 4; z.L = look; z.ca = z.cb = -1;
+            by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_prune_init_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); });
+            return;
+        }
         by_dim(D, [&](auto d) {
             constexpr int DV = decltype(d)::value;
             hipLaunchKernelGGL((sp_prune_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
@@ -2687,7 +3331,19 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
         hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
         if (tail_err == hipSuccess) tail_err = t_prune.stop(st);
     };
-    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail))) return rc;
+    const CovPost post = [&](hipStream_t st, SparseSolver &sp, const GraphBufs &gb, int *bad, const std::vector<int32_t> &pos) -> int {
+        const dim3 per_cand((unsigned)((n + 3) / 4));
+        return greedy_lazy_rounds(st, sp, gb, bad, pos, *lazy, look, sa, sb, kk, (int32_t *)dctl.p, z, t_prune, stats.solve, err, errlen,
+            [&] {
+                by_dim(D, [&](auto d) {
+                    hipLaunchKernelGGL((sp_prune_argmin_kernel<decltype(d)::value>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
+                    hipLaunchKernelGGL((sp_prune_rank_kernel<decltype(d)::value>), dim3(1), dim3(256), 0, st, a, z);
+                });
+            },
+            [&] { by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_prune_round_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); }); },
+            [&] { hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a); });
+    };
+    if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail, lazy ? &post : nullptr))) return rc;
     HIPCHK(tail_err);
     float ms = 0;
     HIPCHK(t_prune.ms(ms));

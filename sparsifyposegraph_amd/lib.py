@@ -85,6 +85,8 @@ SYMBOLS = {
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "spg_ctx_set_factor_descent": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "spg_ctx_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(abi.PcgStats)]),
+    "spg_ctx_set_greedy_method": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "spg_ctx_greedy_stats": (C.c_int, [C.c_void_p, C.POINTER(abi.GreedyStats)]),
     "spg_sparse_plan": (C.c_int, [C.c_int, _i32p, _i32p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.POINTER(abi.SparsePlanInfo),
                                   _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int64]),
     "spg_graph_optimize": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(abi.OptimizeStats)]),
@@ -225,6 +227,19 @@ class Context:
         """spg_ctx_pcg_stats: PCG counters of the context's last optimize call (all zero if it did not run PCG)."""
         st = abi.PcgStats()
         check(self.L.spg_ctx_pcg_stats(self.h, C.byref(st)), self.h, "spg_ctx_pcg_stats")
+        return st.asdict()
+
+    def set_greedy_method(self, method, lookahead=0):
+        """spg_ctx_set_greedy_method: abi.GREEDY_JOINT (default: the joint covariance of all endpoints, at most 46 000
+        variables), GREEDY_LAZY (covariance columns solved round by round into a column cache, no bound) or GREEDY_AUTO
+        (JOINT where it fits, else LAZY) for selectCandidates / pruneCandidates / pruneEdges of this context's graphs.
+        lookahead: candidates whose endpoint columns one panel holds; 0 = a full panel, 1 = the chosen one only."""
+        check(self.L.spg_ctx_set_greedy_method(self.h, int(method), int(lookahead)), self.h, "spg_ctx_set_greedy_method")
+
+    def greedy_stats(self):
+        """spg_ctx_greedy_stats: counters of the context's last select / prune call (all zero before any)."""
+        st = abi.GreedyStats()
+        check(self.L.spg_ctx_greedy_stats(self.h, C.byref(st)), self.h, "spg_ctx_greedy_stats")
         return st.asdict()
 
     def synchronize(self):

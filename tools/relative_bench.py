@@ -19,7 +19,12 @@ plus noise, Omega of an existing edge), so the column-solve part is the same and
 device_seconds and solve_seconds are those of spg_cov_solve_stats (HIP events: factorisation, column solves, selected
 inverse, assembly and, for score / relative, sp_relative_kernel); wall_seconds is the host clock around the whole call
 (plan, staging, uploads, the device work and the copy of the results). Medians over --runs calls after one warm-up call;
-min and max are given beside them."""
+min and max are given beside them.
+
+--method joint|lazy [--lookahead L] (select and prune): how the greedy call gets at Sigma (spg_ctx_set_greedy_method); the
+line then carries spg_greedy_stats of the last run (method, lookahead, column_vertices, column_hits, rhs batches of the
+rounds, round_solve_seconds, refactorised, cache_bytes). --skip-select (prune): do not time the selection twin, which
+needs relativeCovariances of every candidate pair first."""
 import argparse
 import json
 import os
@@ -43,9 +48,19 @@ ap.add_argument("--poses", type=int, default=100000)
 ap.add_argument("--ring", type=int, default=400)
 ap.add_argument("--vertex", type=int, default=50000)
 ap.add_argument("--runs", type=int, default=5)
+ap.add_argument("--method", choices=("joint", "lazy"), default="joint")
+ap.add_argument("--lookahead", type=int, default=0)
+ap.add_argument("--skip-select", action="store_true")
 args = ap.parse_args()
 
 ctx = Context(0)
+ctx.set_greedy_method({"joint": 0, "lazy": 1}[args.method], args.lookahead)
+
+
+def greedy_extra():
+    return {"method": args.method, **{"greedy_" + k: v for k, v in ctx.greedy_stats().items() if k != "method"}}
+
+
 g = g2o_io.synth_sphere(args.poses, args.ring)
 hg = GraphWrapperHIP.from_dict(g, ctx=ctx)
 ids = hg.vertices()[0]
@@ -69,9 +84,10 @@ if args.mode == "prune":
     eidx = np.array(inside[:args.candidates], np.int32)
     star = np.array([e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]] for k in eidx], np.int32)
     rng = np.random.default_rng(2024)
-    meas = hg.relativeCovariances(star)[0]
-    meas[:, :3] += 0.01 * rng.normal(size=(len(star), 3))
-    info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
+    if not args.skip_select:
+        meas = hg.relativeCovariances(star)[0]
+        meas[:, :3] += 0.01 * rng.normal(size=(len(star), 3))
+        info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
 
     def timed(fn, key):
         fn()   # warm-up
@@ -84,8 +100,18 @@ if args.mode == "prune":
             out["device"].append(st["device_seconds"]); out["solve"].append(st["solve_seconds"]); out[key].append(st[key])
         return r, st, out
     rp, sp, tp = timed(lambda: hg.pruneCandidates(eidx, args.k), "prune_seconds")
-    rs, ss, ts = timed(lambda: hg.selectCandidates(star, meas, info, args.k), "select_seconds")
+    gx = greedy_extra()
     med = statistics.median
+    if args.skip_select:
+        print(json.dumps({
+            "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {len(eidx)} existing edges inside a block of {len(pool)} vertices",
+            "mode": "prune", "k": args.k, "candidates": len(eidx), "runs": args.runs, "rounds": sp["rounds"], "endpoints": sp["endpoints"],
+            "prune_seconds": med(tp["prune_seconds"]), "prune_seconds_min": min(tp["prune_seconds"]), "prune_seconds_max": max(tp["prune_seconds"]),
+            "device_seconds": med(tp["device"]), "device_seconds_min": min(tp["device"]), "device_seconds_max": max(tp["device"]),
+            "solve_seconds": med(tp["solve"]), "wall_seconds": med(tp["wall"]), "columns": sp["columns"], "rhs_batches": sp["rhs_batches"],
+            "kld": float(rp["kld"][-1]) if len(rp["kld"]) else 0.0, "bridges": int((rp["status"] == 2).sum()), **gx}), flush=True)
+        sys.exit(0)
+    rs, ss, ts = timed(lambda: hg.selectCandidates(star, meas, info, args.k), "select_seconds")
     print(json.dumps({
         "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {len(eidx)} existing edges inside a block of {len(pool)} vertices",
         "mode": "prune", "k": args.k, "candidates": len(eidx), "runs": args.runs, "rounds": sp["rounds"], "endpoints": sp["endpoints"],
@@ -96,7 +122,7 @@ if args.mode == "prune":
         "select_rounds": ss["rounds"], "select_endpoints": ss["endpoints"], "select_seconds": med(ts["select_seconds"]),
         "select_seconds_min": min(ts["select_seconds"]), "select_seconds_max": max(ts["select_seconds"]),
         "select_device_seconds": med(ts["device"]), "select_solve_seconds": med(ts["solve"]), "select_wall_seconds": med(ts["wall"]),
-        "select_columns": ss["columns"], "prune_over_select": med(tp["prune_seconds"]) / med(ts["select_seconds"])}), flush=True)
+        "select_columns": ss["columns"], "prune_over_select": med(tp["prune_seconds"]) / med(ts["select_seconds"]), **gx}), flush=True)
     sys.exit(0)
 info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
 meas = None
@@ -137,7 +163,7 @@ extra = {}
 if args.mode == "select":
     extra = {"k": args.k, "rounds": s["rounds"], "endpoints": s["endpoints"], "select_seconds": statistics.median(sel),
              "select_seconds_min": min(sel), "select_seconds_max": max(sel), "score_device_seconds": score_dev[-1],
-             "k_rescorings_device_seconds": args.k * score_dev[-1]}
+             "k_rescorings_device_seconds": args.k * score_dev[-1], **greedy_extra()}
 what = f"vertex {v0} against all others" if args.mode != "select" else f"{len(star)} random far pairs over a pool of {len(pool)} vertices"
 print(json.dumps({
     "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {what}", "mode": args.mode, **extra,
