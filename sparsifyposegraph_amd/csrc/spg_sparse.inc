@@ -851,10 +851,38 @@ __device__ __forceinline__ void sel_load_sigma(int lane, const double *joint, lo
         S[k] = (br < 0 || bc < 0) ? 0.0 : joint[((long long)br * D + rr) * ld + (long long)bc * D + cc];
     }
 }
-// One wavefront per candidate, four per workgroup, the LDS slice of sp_relative_kernel: J, L, C_ii(0) = P, gain_i(0), d2
-// and the state (Omega not PD: 1; max_d2 > 0 and d2 > max_d2: 2; else 0).
+// The second source of Sigma (SPG_GREEDY_LAZY, DESIGN 5g-L): no joint block. Round 0 reads the candidate's own 2D x 2D
+// pair block (pslot, the blocks of sp_relative_kernel); a round reads the four blocks Sigma(a_i | b_i, a* | b*) from the
+// two cache strips of the chosen candidate's endpoints. A strip is Sigma[S, v]: m D x D, row-major, strip_len = m D^2
+// doubles, rows in the order of the endpoint slots sa / sb. The init and round kernels of selection and pruning are
+// templates over the source (LAZY) and differ in the statement that loads Sigma alone; the joint forms get a LazyArgs
+// they do not read. rank[0] = i* of the round, rank[1..L) = the next-best eligible candidates in the order of the argmax
+// / argmin (-1: none), the endpoints the host may solve ahead.
+struct LazyArgs {
+    const double *blocks;     // per pair slot (2D)^2, row-major
+    const int32_t *pslot;     // per candidate: its pair block
+    const double *cache;      // the strips
+    long long strip_len;
+    int32_t *rank;            // L entries
+    int L;
+    int ca, cb;               // round kernels: the strips of a*, b* (-1: the fixed vertex)
+};
+// the 2D x 2D block [[S(ra, a*), S(ra, b*)], [S(rb, a*), S(rb, b*)]] out of the strips ca, cb into LDS
 template <int D>
-__global__ __launch_bounds__(256) void sp_select_init_kernel(SelArgs a) {
+__device__ __forceinline__ void lazy_load_sigma(int lane, const double *cache, long long strip_len, int ra, int rb, int ca, int cb, double *S) {
+    constexpr int W = 2 * D;
+    for (int k = lane; k < W * W; k += 64) {
+        const int r = k / W, c = k - r * W;
+        const int br = r < D ? ra : rb, bc = c < D ? ca : cb;
+        const int rr = r < D ? r : r - D, cc = c < D ? c : c - D;
+        S[k] = (br < 0 || bc < 0) ? 0.0 : cache[(long long)bc * strip_len + ((long long)br * D + rr) * D + cc];
+    }
+}
+// One wavefront per candidate, four per workgroup, the LDS slice of sp_relative_kernel: J, L, C_ii(0) = P, gain_i(0), d2
+// and the state (Omega not PD: 1; max_d2 > 0 and d2 > max_d2: 2; else 0). Sigma: the candidate's own block of the joint
+// covariance, or (LAZY) its pair block.
+template <int D, bool LAZY>
+__global__ __launch_bounds__(256) void sp_select_init_kernel(SelArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3, TRI = D * (D + 1) / 2, REC = PS + TRI;
     constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
     __shared__ double lds[4 * PER];
@@ -865,7 +893,12 @@ __global__ __launch_bounds__(256) void sp_select_init_kernel(SelArgs a) {
     double *A = T, *M = T + DD;
     const double *rec = act ? a.rec + (long long)i * REC : nullptr;
     if (act) {
-        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        if constexpr (LAZY) {
+            const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
+            for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
+        } else {
+            sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        }
         if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.va[i], a.vb[i], rec, nullptr, Ja, Jb, e);
     }
     __syncthreads();
@@ -902,21 +935,37 @@ __global__ __launch_bounds__(256) void sp_select_init_kernel(SelArgs a) {
 }
 // (gain descending, index ascending): the order of the argmax, independent of the grid
 __device__ __forceinline__ bool sel_better(double ga, int ia, double gb, int ib) { return ga > gb || (ga == gb && ia < ib); }
-__device__ __forceinline__ void sel_reduce(double &g, int &i, double *sg, int *si) {
+// the best (value, index) of a workgroup of 256 under the order `better` (sel_better / prn_better), to every thread
+template <bool (*better)(double, int, double, int)>
+__device__ __forceinline__ void best_reduce(double &g, int &i, double *sg, int *si) {
     const int t = threadIdx.x;
     sg[t] = g; si[t] = i;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
-        if (t < h && sel_better(sg[t + h], si[t + h], sg[t], si[t])) { sg[t] = sg[t + h]; si[t] = si[t + h]; }
+        if (t < h && better(sg[t + h], si[t + h], sg[t], si[t])) { sg[t] = sg[t + h]; si[t] = si[t + h]; }
         __syncthreads();
     }
     g = sg[0]; i = si[0];
 }
-// Stage 1 (pick == 0, np workgroups): the best (gain, index) of the candidates in state 0 per workgroup into pg / pi.
-// Stage 2 (pick == 1, one workgroup): the best of the partials; none, or a gain below min_gain: ctl[1] = 1. Else i* is
-// appended to sel / cg, marked selected, and its C_ii is published for the round kernel.
-template <int D>
-__global__ __launch_bounds__(256) void sp_select_argmax_kernel(SelArgs a, int pick) {
+// Stage 1 of the argmax (np workgroups): the best (gain, index) of the candidates in state 0 per workgroup into pg / pi.
+__global__ __launch_bounds__(256) void sp_select_argmax_kernel(SelArgs a) {
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    const int stop = a.ctl[1];   // nothing in this kernel writes ctl
+    double g = -__builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop)
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256)
+            if (a.state[i] == 0 && sel_better(a.gain[i], i, g, bi)) { g = a.gain[i]; bi = i; }
+    best_reduce<sel_better>(g, bi, sg, si);
+    if (!stop && threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
+}
+// Stage 2 (one workgroup): the best of the partials; none, or a gain below min_gain: ctl[1] = 1. Else i* is appended to
+// sel / cg, marked selected, and its C_ii is published for the round kernel. RANK (the lazy rounds) adds the ranked list:
+// L - 1 passes over the candidates in state 0, each taking the best one that comes after the previous in the order of
+// sel_better: no atomics, independent of the grid of stage 1.
+template <int D, bool RANK>
+__global__ __launch_bounds__(256) void sp_select_pick_kernel(SelArgs a, LazyArgs z) {
     constexpr int DD = D * D;
     __shared__ double sg[256];
     __shared__ int si[256];
@@ -924,21 +973,11 @@ __global__ __launch_bounds__(256) void sp_select_argmax_kernel(SelArgs a, int pi
     const int stop = a.ctl[1];   // read by every thread before the first barrier; written after it by thread 0 alone
     double g = -__builtin_inf();
     int bi = 0x7fffffff;
-    if (!stop) {
-        if (!pick) {
-            for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256)
-                if (a.state[i] == 0 && sel_better(a.gain[i], i, g, bi)) { g = a.gain[i]; bi = i; }
-        } else {
-            for (int p = threadIdx.x; p < a.np; p += 256)
-                if (sel_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
-        }
-    }
-    sel_reduce(g, bi, sg, si);
+    if (!stop)
+        for (int p = threadIdx.x; p < a.np; p += 256)
+            if (sel_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+    best_reduce<sel_better>(g, bi, sg, si);
     if (stop) return;
-    if (!pick) {
-        if (threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
-        return;
-    }
     if (threadIdx.x == 0) {
         if (bi == 0x7fffffff || g < a.min_gain) {
             a.ctl[1] = 1;
@@ -952,13 +991,34 @@ __global__ __launch_bounds__(256) void sp_select_argmax_kernel(SelArgs a, int pi
             a.state[bi] = 3;
             chosen = bi;
         }
+        if constexpr (RANK) z.rank[0] = chosen;
     }
     __syncthreads();
-    if (chosen >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)chosen * DD + threadIdx.x];
+    const int ch = chosen;
+    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
+    if constexpr (RANK) {
+        double pg = g;
+        int pi = ch >= 0 ? bi : 0x7fffffff;
+        for (int r = 1; r < z.L; r++) {
+            double ng = -__builtin_inf();
+            int ni = 0x7fffffff;
+            if (pi != 0x7fffffff)
+                for (int i = threadIdx.x; i < a.n; i += 256) {
+                    if (a.state[i] != 0) continue;
+                    const double gi = a.gain[i];
+                    if (sel_better(pg, pi, gi, i) && sel_better(gi, i, ng, ni)) { ng = gi; ni = i; }
+                }
+            __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
+            best_reduce<sel_better>(ng, ni, sg, si);
+            if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
+            pg = ng; pi = ni;
+        }
+    }
 }
-// Conditions every candidate still in state 0, and i* itself, on i* (read from ctl). One wavefront per candidate.
-template <int D>
-__global__ __launch_bounds__(256) void sp_select_round_kernel(SelArgs a) {
+// Conditions every candidate still in state 0, and i* itself, on i* (read from ctl). One wavefront per candidate. Sigma:
+// the block (a_i | b_i, a* | b*) of the joint covariance, or (LAZY) of the strips z.ca, z.cb.
+template <int D, bool LAZY>
+__global__ __launch_bounds__(256) void sp_select_round_kernel(SelArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D;
     constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
     __shared__ double lds[4 * PER];
@@ -969,7 +1029,8 @@ __global__ __launch_bounds__(256) void sp_select_round_kernel(SelArgs a) {
     double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
            *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD, *y = Ci + DD;
     if (act) {
-        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
+        if constexpr (LAZY) lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
+        else sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
         for (int k = lane; k < 2 * DD; k += 64) {
             Ji[k] = a.J[(long long)i * 2 * DD + k];
             Js[k] = a.J[(long long)s * 2 * DD + k];
@@ -1124,9 +1185,9 @@ __device__ __forceinline__ bool rel_chol_downdate(double *M, double min_margin, 
     return ok;
 }
 // One wavefront per candidate, four per workgroup, the LDS slice of sp_select_init_kernel: J, L, C_ii(0) = P, tr0, the
-// loss and the margin of round 0, and the state (Omega not finite or not PD: 1, else 0).
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a) {
+// loss and the margin of round 0, and the state (Omega not finite or not PD: 1, else 0). Sigma: as there.
+template <int D, bool LAZY>
+__global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3;
     constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
     __shared__ double lds[4 * PER];
@@ -1138,7 +1199,12 @@ __global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a) {
     const spg_edge_ref *er = act ? a.er + a.eidx[i] : nullptr;
     const double *rec = act ? a.arena + er->off : nullptr;
     if (act) {
-        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        if constexpr (LAZY) {
+            const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
+            for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
+        } else {
+            sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[i], a.sb[i], S);
+        }
         if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.ev[er->vbegin], a.ev[er->vbegin + 1], rec, nullptr, Ja, Jb, e);
     }
     __syncthreads();
@@ -1178,22 +1244,27 @@ __global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a) {
 }
 // (loss ascending, index ascending): the order of the argmin, independent of the grid
 __device__ __forceinline__ bool prn_better(double ga, int ia, double gb, int ib) { return ga < gb || (ga == gb && ia < ib); }
-__device__ __forceinline__ void prn_reduce(double &g, int &i, double *sg, int *si) {
-    const int t = threadIdx.x;
-    sg[t] = g; si[t] = i;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h && prn_better(sg[t + h], si[t + h], sg[t], si[t])) { sg[t] = sg[t + h]; si[t] = si[t + h]; }
-        __syncthreads();
-    }
-    g = sg[0]; i = si[0];
+// Stage 1 of the argmin (np workgroups): the best (loss, index) per workgroup of the candidates in state 0 that are
+// eligible this round (a loss that is not NaN, margin >= min_margin; the others stay in state 0) into pg / pi.
+__global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a) {
+    __shared__ double sg[256];
+    __shared__ int si[256];
+    const int stop = a.ctl[1];   // nothing in this kernel writes ctl
+    double g = __builtin_inf();
+    int bi = 0x7fffffff;
+    if (!stop)
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256) {
+            const double l = a.loss[i];
+            if (a.state[i] == 0 && l == l && a.margin[i] >= a.min_margin && prn_better(l, i, g, bi)) { g = l; bi = i; }
+        }
+    best_reduce<prn_better>(g, bi, sg, si);
+    if (!stop && threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
 }
-// Stage 1 (pick == 0, np workgroups): the best (loss, index) per workgroup of the candidates in state 0 that are eligible
-// this round (a loss that is not NaN, margin >= min_margin; the others stay in state 0) into pg / pi. Stage 2 (pick == 1,
-// one workgroup): the best of the partials; none, a loss above max_loss or a cumulative KLD above max_kld: ctl[1] = 1.
-// Else i* is appended to sel / cl / ck, marked pruned, and its C_ii is published for the round kernel.
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a, int pick) {
+// Stage 2 (one workgroup): the best of the partials; none, a loss above max_loss or a cumulative KLD above max_kld:
+// ctl[1] = 1. Else i* is appended to sel / cl / ck, marked pruned, and its C_ii is published for the round kernel. RANK
+// (the lazy rounds) adds the ranked list over the candidates eligible this round, in the order of prn_better.
+template <int D, bool RANK>
+__global__ __launch_bounds__(256) void sp_prune_pick_kernel(PruneArgs a, LazyArgs z) {
     constexpr int DD = D * D;
     __shared__ double sg[256];
     __shared__ int si[256];
@@ -1201,23 +1272,11 @@ __global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a, int p
     const int stop = a.ctl[1];   // read by every thread before the first barrier; written after it by thread 0 alone
     double g = __builtin_inf();
     int bi = 0x7fffffff;
-    if (!stop) {
-        if (!pick) {
-            for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256) {
-                const double l = a.loss[i];
-                if (a.state[i] == 0 && l == l && a.margin[i] >= a.min_margin && prn_better(l, i, g, bi)) { g = l; bi = i; }
-            }
-        } else {
-            for (int p = threadIdx.x; p < a.np; p += 256)
-                if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
-        }
-    }
-    prn_reduce(g, bi, sg, si);
+    if (!stop)
+        for (int p = threadIdx.x; p < a.np; p += 256)
+            if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+    best_reduce<prn_better>(g, bi, sg, si);
     if (stop) return;
-    if (!pick) {
-        if (threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
-        return;
-    }
     if (threadIdx.x == 0) {
         chosen = -1;
         if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
@@ -1238,15 +1297,36 @@ __global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a, int p
                 chosen = bi;
             }
         }
+        if constexpr (RANK) z.rank[0] = chosen;
     }
     __syncthreads();
-    if (chosen >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)chosen * DD + threadIdx.x];
+    const int ch = chosen;
+    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
+    if constexpr (RANK) {
+        double pg = g;
+        int pi = ch >= 0 ? bi : 0x7fffffff;
+        for (int r = 1; r < z.L; r++) {
+            double ng = __builtin_inf();
+            int ni = 0x7fffffff;
+            if (pi != 0x7fffffff)
+                for (int i = threadIdx.x; i < a.n; i += 256) {
+                    const double l = a.loss[i];
+                    if (a.state[i] != 0 || !(l == l) || !(a.margin[i] >= a.min_margin)) continue;
+                    if (prn_better(pg, pi, l, i) && prn_better(l, i, ng, ni)) { ng = l; ni = i; }
+                }
+            __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
+            best_reduce<prn_better>(ng, ni, sg, si);
+            if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
+            pg = ng; pi = ni;
+        }
+    }
 }
 // Conditions every candidate still in state 0, and i* itself, on the removal of i* (read from ctl), then re-evaluates the
 // candidate's own M, loss and margin. One wavefront per candidate. M of i* passed the margin test when it was picked; if
 // its factorisation fails all the same, the candidate gets a NaN loss and margin and nothing else of it is touched.
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a) {
+// Sigma: as in sp_select_round_kernel.
+template <int D, bool LAZY>
+__global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D;
     constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
     __shared__ double lds[4 * PER];
@@ -1258,7 +1338,8 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a) {
     double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
            *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD;
     if (act) {
-        sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
+        if constexpr (LAZY) lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
+        else sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
         for (int k = lane; k < 2 * DD; k += 64) {
             Ji[k] = a.J[(long long)i * 2 * DD + k];
             Js[k] = a.J[(long long)s * 2 * DD + k];
@@ -1355,36 +1436,9 @@ __global__ __launch_bounds__(256) void sp_prune_gather_kernel(PruneArgs a) {
     a.status[i] = st != 0 ? st : kept ? 0 : 2;
 }
 
-// ---- lazy forms of the selection and pruning kernels (SPG_GREEDY_LAZY, DESIGN 5g-L): no joint block. Round 0 reads the
-// candidate's own 2D x 2D pair block (pslot, the blocks of sp_relative_kernel); a round reads the four blocks
-// Sigma(a_i | b_i, a* | b*) from the two cache strips of the chosen candidate's endpoints. A strip is Sigma[S, v]: m D x D,
-// row-major, strip_len = m D^2 doubles, rows in the order of the endpoint slots sa / sb. Everything after the load is the
-// text of the joint kernels above, which keep theirs (see the note at rel_geometry): a change to one has to be made in
-// the other. ctl[0..2] as above; rank[0] = i* of the round, rank[1..L) = the next-best eligible candidates in the order
-// of the argmax / argmin (-1: none), the endpoints the host may solve ahead.
-struct LazyArgs {
-    const double *blocks;     // per pair slot (2D)^2, row-major
-    const int32_t *pslot;     // per candidate: its pair block
-    const double *cache;      // the strips
-    long long strip_len;
-    int32_t *rank;            // L entries
-    int L;
-    int ca, cb;               // round kernels: the strips of a*, b* (-1: the fixed vertex)
-};
-// the 2D x 2D block [[S(ra, a*), S(ra, b*)], [S(rb, a*), S(rb, b*)]] out of the strips ca, cb into LDS
-template <int D>
-__device__ __forceinline__ void lazy_load_sigma(int lane, const double *cache, long long strip_len, int ra, int rb, int ca, int cb, double *S) {
-    constexpr int W = 2 * D;
-    for (int k = lane; k < W * W; k += 64) {
-        const int r = k / W, c = k - r * W;
-        const int br = r < D ? ra : rb, bc = c < D ? ca : cb;
-        const int rr = r < D ? r : r - D, cc = c < D ? c : c - D;
-        S[k] = (br < 0 || bc < 0) ? 0.0 : cache[(long long)bc * strip_len + ((long long)br * D + rr) * D + cc];
-    }
-}
-// cache[strip[c]][(j D + r) D + cc] = ws[srow[j] + r R + D c + cc]: the solved panel rows of every endpoint vertex j
-// (srow: where its first row starts in the panel workspace) into the strips of the panel's ncol column vertices.
-// One thread per element, the D ncol panel columns fastest; every strip element has one writer.
+// Fills the strips of LazyArgs: cache[strip[c]][(j D + r) D + cc] = ws[srow[j] + r R + D c + cc], the solved panel rows
+// of every endpoint vertex j (srow: where its first row starts in the panel workspace) into the strips of the panel's
+// ncol column vertices. One thread per element, the D ncol panel columns fastest; every strip element has one writer.
 __global__ __launch_bounds__(256) void sp_strip_rows_kernel(const double *ws, const int64_t *srow, int m, int D, int R, const int32_t *strip, int ncol,
                                                              long long strip_len, double *cache) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)D * ncol;
@@ -1393,404 +1447,6 @@ __global__ __launch_bounds__(256) void sp_strip_rows_kernel(const double *ws, co
     const int e = (int)(idx - row * per), c = e / D, cc = e - c * D;
     const int j = (int)(row / D), r = (int)(row - (long long)j * D);
     cache[(long long)strip[c] * strip_len + row * D + cc] = ws[srow[j] + (long long)r * R + e];
-}
-template <int D>
-__global__ __launch_bounds__(256) void sp_select_init_lazy_kernel(SelArgs a, LazyArgs z) {
-    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3, TRI = D * (D + 1) / 2, REC = PS + TRI;
-    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
-    __shared__ double lds[4 * PER];
-    __shared__ int okv[4];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
-    const bool act = i < a.n;
-    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
-    double *A = T, *M = T + DD;
-    const double *rec = act ? a.rec + (long long)i * REC : nullptr;
-    if (act) {
-        const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
-        for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
-        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.va[i], a.vb[i], rec, nullptr, Ja, Jb, e);
-    }
-    __syncthreads();
-    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
-    __syncthreads();
-    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
-    if (act && lane == 0) {
-        double chi;
-        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
-    }
-    __syncthreads();
-    const bool go = act && okv[w];
-    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
-    __syncthreads();
-    if (go && lane < DD) rel_M<D>(lane, L, A, M);
-    __syncthreads();
-    if (act && lane == 0) {
-        double gain = __builtin_nan(""), d2 = gain;
-        int st = 1;
-        if (go) {
-            rel_chol_M<D>(M, y, gain, d2);
-            st = (a.max_d2 > 0.0 && !(d2 <= a.max_d2)) ? 2 : 0;
-        }
-        a.gain[i] = gain;
-        a.d2[i] = d2;
-        a.state[i] = st;
-    }
-    if (act && lane < DD) {
-        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
-        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
-        a.L[(long long)i * DD + lane] = L[lane];
-        a.C[(long long)i * DD + lane] = P[lane];
-    }
-}
-// Stage 2 of the argmax, lazy form (one workgroup, after stage 1 of sp_select_argmax_kernel): the same choice and the same
-// bookkeeping, then L - 1 passes over the candidates in state 0, each taking the best one that comes after the previous
-// in the order of sel_better: no atomics, independent of the grid of stage 1.
-template <int D>
-__global__ __launch_bounds__(256) void sp_select_rank_kernel(SelArgs a, LazyArgs z) {
-    constexpr int DD = D * D;
-    __shared__ double sg[256];
-    __shared__ int si[256];
-    __shared__ int chosen;
-    const int stop = a.ctl[1];
-    double g = -__builtin_inf();
-    int bi = 0x7fffffff;
-    if (!stop)
-        for (int p = threadIdx.x; p < a.np; p += 256)
-            if (sel_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
-    sel_reduce(g, bi, sg, si);
-    if (stop) return;
-    if (threadIdx.x == 0) {
-        if (bi == 0x7fffffff || g < a.min_gain) {
-            a.ctl[1] = 1;
-            chosen = -1;
-        } else {
-            const int c = a.ctl[0];
-            a.sel[c] = bi;
-            a.cg[c] = g;
-            a.ctl[0] = c + 1;
-            a.ctl[2] = bi;
-            a.state[bi] = 3;
-            chosen = bi;
-        }
-        z.rank[0] = chosen;
-    }
-    __syncthreads();
-    const int ch = chosen;
-    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
-    double pg = g;
-    int pi = ch >= 0 ? bi : 0x7fffffff;
-    for (int r = 1; r < z.L; r++) {
-        double ng = -__builtin_inf();
-        int ni = 0x7fffffff;
-        if (pi != 0x7fffffff)
-            for (int i = threadIdx.x; i < a.n; i += 256) {
-                if (a.state[i] != 0) continue;
-                const double gi = a.gain[i];
-                if (sel_better(pg, pi, gi, i) && sel_better(gi, i, ng, ni)) { ng = gi; ni = i; }
-            }
-        __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
-        sel_reduce(ng, ni, sg, si);
-        if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
-        pg = ng; pi = ni;
-    }
-}
-template <int D>
-__global__ __launch_bounds__(256) void sp_select_round_lazy_kernel(SelArgs a, LazyArgs z) {
-    constexpr int W = 2 * D, DD = D * D;
-    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
-    __shared__ double lds[4 * PER];
-    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
-    const int s = a.ctl[2], t = a.ctl[0] - 1;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
-    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
-    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
-           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD, *y = Ci + DD;
-    if (act) {
-        lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
-        for (int k = lane; k < 2 * DD; k += 64) {
-            Ji[k] = a.J[(long long)i * 2 * DD + k];
-            Js[k] = a.J[(long long)s * 2 * DD + k];
-        }
-        if (lane < DD) {
-            Ls[lane] = a.L[(long long)s * DD + lane];
-            Ms[lane] = a.pubC[lane];
-            Li[lane] = a.L[(long long)i * DD + lane];
-            Ci[lane] = a.C[(long long)i * DD + lane];
-        }
-        if (lane < D) y[lane] = 0.0;
-    }
-    __syncthreads();
-    if (act) {
-        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
-        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
-    }
-    __syncthreads();
-    if (act && lane < DD) {
-        rel_M<D>(lane, Ls, As, Ms);                    // M = I + L*^T C** L*
-        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
-        double x = 0;
-        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
-        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
-        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
-        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
-            double d = 0;
-            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
-            x -= d;
-        }
-        X[lane] = x;
-    }
-    __syncthreads();
-    if (act && lane == 0) {
-        double g, d2;
-        rel_chol_M<D>(Ms, y, g, d2);                   // G in the lower triangle of Ms
-    }
-    __syncthreads();
-    if (act && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
-        const int r = lane;
-        for (int j = 0; j < D; j++) {
-            double v = (j <= r) ? Ls[r * D + j] : 0.0;
-            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
-            K[r * D + j] = v / Ms[j * D + j];
-        }
-    }
-    __syncthreads();
-    if (act && lane < DD) {                            // B_i,t = X K, appended to the history
-        const int r = lane / D, c = lane - r * D;
-        double v = 0;
-        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
-        B[lane] = v;
-        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
-    }
-    __syncthreads();
-    if (act && lane < DD) {                            // C_ii -= B B^T, r <= c, mirrored
-        const int r = lane / D, c = lane - r * D;
-        if (r <= c) {
-            double d = 0;
-            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
-            const double v = Ci[r * D + c] - d;
-            Ci[r * D + c] = v;
-            Ci[c * D + r] = v;
-        }
-    }
-    __syncthreads();
-    if (act && lane < DD) {
-        a.C[(long long)i * DD + lane] = Ci[lane];
-        if (go) rel_PL<D>(lane, Ci, Li, As);
-    }
-    __syncthreads();
-    if (go && lane < DD) rel_M<D>(lane, Li, As, Ms);
-    __syncthreads();
-    if (go && lane == 0) {
-        double g, d2;
-        rel_chol_M<D>(Ms, y, g, d2);
-        a.gain[i] = g;
-    }
-}
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_init_lazy_kernel(PruneArgs a, LazyArgs z) {
-    constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3;
-    constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
-    __shared__ double lds[4 * PER];
-    __shared__ int okv[4];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
-    const bool act = i < a.n;
-    double *S = lds + w * PER, *Ja = S + W * W, *Jb = Ja + DD, *T = Jb + DD, *P = T + D * W, *L = P + DD, *e = L + DD, *y = e + D;
-    double *A = T, *M = T + DD;
-    const spg_edge_ref *er = act ? a.er + a.eidx[i] : nullptr;
-    const double *rec = act ? a.arena + er->off : nullptr;
-    if (act) {
-        const double *blk = z.blocks + (long long)z.pslot[i] * W * W;
-        for (int k = lane; k < W * W; k += 64) S[k] = blk[k];
-        if (lane == 0) rel_geometry<D>(a.arena, a.vpo, a.ev[er->vbegin], a.ev[er->vbegin + 1], rec, nullptr, Ja, Jb, e);
-    }
-    __syncthreads();
-    if (act) rel_J_sigma<D>(lane, Ja, Jb, S, T);
-    __syncthreads();
-    if (act && lane < DD) rel_P<D>(lane, T, Ja, Jb, P, nullptr);
-    if (act && lane == 0) {
-        double chi;
-        okv[w] = rel_omega<D>(rec + PS, e, L, y, chi);
-    }
-    __syncthreads();
-    const bool go = act && okv[w];
-    if (go && lane < DD) rel_PL<D>(lane, P, L, A);
-    __syncthreads();
-    if (go && lane == 0) {           // tr(L^T P L) before M takes A's neighbour
-        double tr = 0;
-        for (int c = 0; c < D; c++)
-            for (int t = c; t < D; t++) tr += L[t * D + c] * A[t * D + c];
-        a.tr0[i] = tr;
-    }
-    if (go && lane < DD) rel_M_down<D>(lane, L, A, M);
-    __syncthreads();
-    if (act && lane == 0) {
-        double loss = __builtin_nan(""), margin = loss;
-        if (go) rel_chol_downdate<D>(M, a.min_margin, loss, margin);
-        else a.tr0[i] = loss;
-        a.loss[i] = loss;
-        a.margin[i] = margin;
-        a.state[i] = go ? 0 : 1;
-    }
-    if (act && lane < DD) {
-        a.J[(long long)i * 2 * DD + lane] = Ja[lane];
-        a.J[(long long)i * 2 * DD + DD + lane] = Jb[lane];
-        a.L[(long long)i * DD + lane] = L[lane];
-        a.C[(long long)i * DD + lane] = P[lane];
-    }
-}
-// Stage 2 of the argmin, lazy form: the choice, stop rules and bookkeeping of sp_prune_argmin_kernel(pick = 1), then the
-// ranked list over the candidates eligible this round, in the order of prn_better.
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_rank_kernel(PruneArgs a, LazyArgs z) {
-    constexpr int DD = D * D;
-    __shared__ double sg[256];
-    __shared__ int si[256];
-    __shared__ int chosen;
-    const int stop = a.ctl[1];
-    double g = __builtin_inf();
-    int bi = 0x7fffffff;
-    if (!stop)
-        for (int p = threadIdx.x; p < a.np; p += 256)
-            if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
-    prn_reduce(g, bi, sg, si);
-    if (stop) return;
-    if (threadIdx.x == 0) {
-        chosen = -1;
-        if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
-            a.ctl[1] = 1;
-        } else {
-            const double kld = a.kldsum[0] + (g - 0.5 * a.tr0[bi]);
-            if (a.max_kld > 0.0 && kld > a.max_kld) {
-                a.ctl[1] = 1;
-            } else {
-                const int c = a.ctl[0];
-                a.sel[c] = bi;
-                a.cl[c] = g;
-                a.ck[c] = kld;
-                a.kldsum[0] = kld;
-                a.ctl[0] = c + 1;
-                a.ctl[2] = bi;
-                a.state[bi] = 3;
-                chosen = bi;
-            }
-        }
-        z.rank[0] = chosen;
-    }
-    __syncthreads();
-    const int ch = chosen;
-    if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
-    double pg = g;
-    int pi = ch >= 0 ? bi : 0x7fffffff;
-    for (int r = 1; r < z.L; r++) {
-        double ng = __builtin_inf();
-        int ni = 0x7fffffff;
-        if (pi != 0x7fffffff)
-            for (int i = threadIdx.x; i < a.n; i += 256) {
-                const double l = a.loss[i];
-                if (a.state[i] != 0 || !(l == l) || !(a.margin[i] >= a.min_margin)) continue;
-                if (prn_better(pg, pi, l, i) && prn_better(l, i, ng, ni)) { ng = l; ni = i; }
-            }
-        __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
-        prn_reduce(ng, ni, sg, si);
-        if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
-        pg = ng; pi = ni;
-    }
-}
-template <int D>
-__global__ __launch_bounds__(256) void sp_prune_round_lazy_kernel(PruneArgs a, LazyArgs z) {
-    constexpr int W = 2 * D, DD = D * D;
-    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
-    __shared__ double lds[4 * PER];
-    __shared__ int okv[4];
-    if (a.ctl[1]) return;   // nothing in this kernel writes ctl
-    const int s = a.ctl[2], t = a.ctl[0] - 1;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, i = blockIdx.x * 4 + w;
-    const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
-    double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
-           *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD;
-    if (act) {
-        lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
-        for (int k = lane; k < 2 * DD; k += 64) {
-            Ji[k] = a.J[(long long)i * 2 * DD + k];
-            Js[k] = a.J[(long long)s * 2 * DD + k];
-        }
-        if (lane < DD) {
-            Ls[lane] = a.L[(long long)s * DD + lane];
-            Ms[lane] = a.pubC[lane];
-            Li[lane] = a.L[(long long)i * DD + lane];
-            Ci[lane] = a.C[(long long)i * DD + lane];
-        }
-    }
-    __syncthreads();
-    if (act) {
-        rel_J_sigma<D>(lane, Ji, Ji + DD, S, T);
-        if (lane < DD) rel_PL<D>(lane, Ms, Ls, As);   // C** L*
-    }
-    __syncthreads();
-    if (act && lane < DD) {
-        rel_M_down<D>(lane, Ls, As, Ms);               // M = I - L*^T C** L*
-        const int r = lane / D, c = lane - r * D;      // X = C_i*(t), every (r, c): it is not symmetric
-        double x = 0;
-        for (int q = 0; q < D; q++) x += T[r * W + q] * Js[c * D + q];
-        for (int q = 0; q < D; q++) x += T[r * W + D + q] * Js[DD + c * D + q];
-        const double *hi = a.hist + (long long)i * a.kk * DD + r * D, *hs = a.hist + (long long)s * a.kk * DD + c * D;
-        for (int u = 0; u < t; u++, hi += DD, hs += DD) {
-            double d = 0;
-            for (int q = 0; q < D; q++) d += hi[q] * hs[q];
-            x += d;
-        }
-        X[lane] = x;
-    }
-    __syncthreads();
-    if (act && lane == 0) {
-        double l, m;
-        okv[w] = rel_chol_downdate<D>(Ms, 0.0, l, m);  // G in the lower triangle of Ms
-        if (!okv[w]) { a.loss[i] = __builtin_nan(""); a.margin[i] = __builtin_nan(""); }
-    }
-    __syncthreads();
-    const bool upd = act && okv[w];
-    if (upd && lane < D) {                             // K = L* G^-T, row `lane`: K G^T = L*
-        const int r = lane;
-        for (int j = 0; j < D; j++) {
-            double v = (j <= r) ? Ls[r * D + j] : 0.0;
-            for (int q = 0; q < j; q++) v -= K[r * D + q] * Ms[j * D + q];
-            K[r * D + j] = v / Ms[j * D + j];
-        }
-    }
-    __syncthreads();
-    if (upd && lane < DD) {                            // B_i,t = X K, appended to the history
-        const int r = lane / D, c = lane - r * D;
-        double v = 0;
-        for (int q = 0; q < D; q++) v += X[r * D + q] * K[q * D + c];
-        B[lane] = v;
-        a.hist[((long long)i * a.kk + t) * DD + lane] = v;
-    }
-    __syncthreads();
-    if (upd && lane < DD) {                            // C_ii += B B^T, r <= c, mirrored
-        const int r = lane / D, c = lane - r * D;
-        if (r <= c) {
-            double d = 0;
-            for (int q = 0; q < D; q++) d += B[r * D + q] * B[c * D + q];
-            const double v = Ci[r * D + c] + d;
-            Ci[r * D + c] = v;
-            Ci[c * D + r] = v;
-        }
-    }
-    __syncthreads();
-    const bool re = upd && go;
-    if (upd && lane < DD) {
-        a.C[(long long)i * DD + lane] = Ci[lane];
-        if (go) rel_PL<D>(lane, Ci, Li, As);
-    }
-    __syncthreads();
-    if (re && lane < DD) rel_M_down<D>(lane, Li, As, Ms);
-    __syncthreads();
-    if (re && lane == 0) {
-        double l, m;
-        rel_chol_downdate<D>(Ms, a.min_margin, l, m);
-        a.loss[i] = l;
-        a.margin[i] = m;
-    }
 }
 
 // Per-vertex KLD of two D x D marginals, kullbackLeiblerDivergence(diff, Sx^-1, Sy^-1, InformationInformation)
@@ -3056,23 +2712,35 @@ int hip_sparse_relative(void *stream, const DenseGraphIn &in, const int32_t *va,
     return 0;
 }
 
-// ---- the lazy mode of the two greedy calls (SPG_GREEDY_LAZY, DESIGN 5g-L)
+// ---- the two greedy calls and their lazy mode (SPG_GREEDY_LAZY, DESIGN 5g-L)
 constexpr int kGreedyCtl = 4 + 16;   // control words, then the ranked list (at most 64 / 2D = 10 candidates)
 
-// the free-HBM check of a lazy call, before anything is allocated; the panel workspace is checked once the plan is known
-static int greedy_lazy_capacity(const char *what, double own_bytes, int64_t blocks_len, int D, int m, char *err, size_t errlen) {
+// by_dim with the LAZY / RANK flag of the greedy kernels as a second compile-time constant: f(d, std::true_type) or false
+template <class F>
+void by_dim_lazy(int D, bool lazy, F &&f) {
+    by_dim(D, [&](auto d) { lazy ? f(d, std::true_type{}) : f(d, std::false_type{}); });
+}
+
+// The free-HBM check of a greedy call, before anything is allocated. bytes: the joint block (a lazy call: the pair
+// blocks), blocks_len doubles, plus the histories and the state; a lazy call adds two column strips, and its panel
+// workspace is checked once the plan is known.
+static int greedy_capacity(const char *what, double bytes, int64_t blocks_len, int D, const GreedyLazyIn *lazy, char *err, size_t errlen) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    const double strips = 2.0 * 8.0 * (double)m * D * D;
-    if (own_bytes + strips + (double)(1ull << 30) <= (double)free_b) return 0;
-    snprintf(err, errlen, "%s (lazy) needs %.2f GB of pair blocks, %.2f GB of histories and state and %.2f GB for two column strips, %.1f GB are free",
-             what, blocks_len * 8e-9, (own_bytes - 8.0 * (double)blocks_len) * 1e-9, strips * 1e-9, free_b * 1e-9);
+    const double strips = lazy ? 2.0 * 8.0 * (double)lazy->m * D * D : 0.0;
+    if (bytes + strips + (double)(1ull << 30) <= (double)free_b) return 0;
+    if (lazy)
+        snprintf(err, errlen, "%s (lazy) needs %.2f GB of pair blocks, %.2f GB of histories and state and %.2f GB for two column strips, %.1f GB are free",
+                 what, blocks_len * 8e-9, (bytes - 8.0 * (double)blocks_len) * 1e-9, strips * 1e-9, free_b * 1e-9);
+    else
+        snprintf(err, errlen, "%s needs %.1f GB for the joint covariance of the endpoints and the histories, %.1f GB are free", what, bytes * 1e-9,
+                 free_b * 1e-9);
     return SPG_ECAPACITY;
 }
 
 // The rounds of a lazy call, after round 0 (init kernel, in the selected inverse's event pair) has been synchronised: the
-// factor is rebuilt (the selected inverse overwrote it), then per round: pick() = argmax / argmin stage 1 and the lazy
-// stage 2; the host reads the control words and the ranked list (one synchronisation), stops on the device's stop word,
+// factor is rebuilt (the selected inverse overwrote it), then per round: pick() = argmax / argmin stage 1 and the
+// ranking stage 2; the host reads the control words and the ranked list (one synchronisation), stops on the device's stop word,
 // lets the planner choose the columns to solve, sweeps them into their strips and launches round() with the strips of
 // a*, b* in z. gather() and the call's timer end the device part.
 template <class Pick, class Round, class Gather>
@@ -3132,7 +2800,7 @@ static int greedy_lazy_rounds(hipStream_t st, SparseSolver &sp, const GraphBufs 
 
 // spg_graph_select_candidates: the sub-block lists describe the m D x m D joint covariance of the candidates' endpoints
 // (joint_len doubles, row stride ld, kept on the device); candidate i has the poses of vertex indices ca[i], cb[i] and
-// the endpoint slots sa[i], sb[i] (-1: the fixed vertex). The tail enqueues init, kk x (argmax, argmax, round) and the
+// the endpoint slots sa[i], sb[i] (-1: the fixed vertex). The tail enqueues init, kk x (argmax, pick, round) and the
 // gather without a synchronisation; the stop rules are device words the later launches return on. selected / cond_gain:
 // kk entries (the tail beyond *nsel is -1 / NaN), final_gain / status: n each, may be nullptr. Host arrays throughout.
 int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
@@ -3143,20 +2811,9 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     const int D = in.D, DD = D * D, PS = D == 6 ? 7 : 3, REC = PS + D * (D + 1) / 2;
     const int np = std::min((n + 255) / 256, 256);
     const int look = lazy ? greedy_lookahead(lazy->lookahead, D) : 0;
-    const double own_bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
+    const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
     int rc = 0;
-    if (lazy) {
-        if ((rc = greedy_lazy_capacity("candidate selection", own_bytes, joint_len, D, lazy->m, err, errlen))) return rc;
-    } else {
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 3));
-        if (bytes + (double)(1ull << 30) > (double)free_b) {
-            snprintf(err, errlen, "candidate selection needs %.1f GB for the joint covariance of the endpoints and the histories, %.1f GB are free",
-                     bytes * 1e-9, free_b * 1e-9);
-            return SPG_ECAPACITY;
-        }
-    }
+    if ((rc = greedy_capacity("candidate selection", bytes, joint_len, D, lazy, err, errlen))) return rc;
     DevBuf djoint, dca, dcb, dsa, dsb, drec, dJ, dL, dC, dhist, dgain, dd2, dstate, dpg, dpi, dctl, dpub, dsel, dcg, dfinal, dpslot;
     if ((rc = upload(dca, ca, (size_t)n, s)) || (rc = upload(dcb, cb, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) ||
         (rc = upload(dsb, sb, (size_t)n, s)) || (rc = upload(drec, rec, (size_t)n * REC, s)) || (lazy && (rc = upload(dpslot, lazy->pslot, (size_t)n, s)))) {
@@ -3184,6 +2841,25 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     hipError_t tail_err = hipSuccess;
     SelArgs a{};
     LazyArgs z{};
+    // the launches of the call, on s (the stream tail and post are handed), once tail has filled a and z
+    const dim3 per_cand((unsigned)((n + 3) / 4)), wg(256);
+    const auto init = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_select_init_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        });
+    };
+    const auto stage1 = [&] { hipLaunchKernelGGL(sp_select_argmax_kernel, dim3((unsigned)np), wg, 0, s, a); };
+    const auto stage2 = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_select_pick_kernel<decltype(d)::value, decltype(lz)::value>), dim3(1), wg, 0, s, a, z);
+        });
+    };
+    const auto round = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_select_round_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        });
+    };
+    const auto gather = [&] { hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), wg, 0, s, a); };
     const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
         a.arena = gb.dev.arena; a.vpo = gb.dev.vpo;
         a.va = (const int32_t *)dca.p; a.vb = (const int32_t *)dcb.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
@@ -3193,37 +2869,20 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
         a.pg = (double *)dpg.p; a.pi = (int32_t *)dpi.p; a.ctl = (int32_t *)dctl.p; a.pubC = (double *)dpub.p;
         a.sel = (int32_t *)dsel.p; a.cg = (double *)dcg.p; a.final_gain = (double *)dfinal.p;
         a.n = n; a.kk = kk; a.np = np; a.min_gain = min_gain; a.max_d2 = max_d2;
-        const dim3 per_cand((unsigned)((n + 3) / 4));
-        tail_err = t_select.start(st);
         if (lazy) {   // round 0 from the pair blocks; the rounds follow in `post`, on the factor
             a.joint = nullptr; a.ld = 0;
             z.blocks = joint; z.pslot = (const int32_t *)dpslot.p; z.rank = (int32_t *)dctl.p + 4; z.L = look; z.ca = z.cb = -1;
-            by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_select_init_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); });
-            return;
         }
-        by_dim(D, [&](auto d) {
-            constexpr int DV = decltype(d)::value;
-            hipLaunchKernelGGL((sp_select_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
-            for (int t = 0; t < kk; t++) {
-                hipLaunchKernelGGL((sp_select_argmax_kernel<DV>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
-                hipLaunchKernelGGL((sp_select_argmax_kernel<DV>), dim3(1), dim3(256), 0, st, a, 1);
-                hipLaunchKernelGGL((sp_select_round_kernel<DV>), per_cand, dim3(256), 0, st, a);
-            }
-        });
-        hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        tail_err = t_select.start(st);
+        init();
+        if (lazy) return;
+        for (int t = 0; t < kk; t++) { stage1(); stage2(); round(); }
+        gather();
         if (tail_err == hipSuccess) tail_err = t_select.stop(st);
     };
     const CovPost post = [&](hipStream_t st, SparseSolver &sp, const GraphBufs &gb, int *bad, const std::vector<int32_t> &pos) -> int {
-        const dim3 per_cand((unsigned)((n + 3) / 4));
         return greedy_lazy_rounds(st, sp, gb, bad, pos, *lazy, look, sa, sb, kk, (int32_t *)dctl.p, z, t_select, stats.solve, err, errlen,
-            [&] {
-                by_dim(D, [&](auto d) {
-                    hipLaunchKernelGGL((sp_select_argmax_kernel<decltype(d)::value>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
-                    hipLaunchKernelGGL((sp_select_rank_kernel<decltype(d)::value>), dim3(1), dim3(256), 0, st, a, z);
-                });
-            },
-            [&] { by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_select_round_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); }); },
-            [&] { hipLaunchKernelGGL(sp_select_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a); });
+                                  [&] { stage1(); stage2(); }, round, gather);
     };
     if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail, lazy ? &post : nullptr))) return rc;
     HIPCHK(tail_err);
@@ -3242,7 +2901,7 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
 }
 
 // spg_graph_prune_candidates: the sub-block lists and slots as hip_sparse_select; candidate i is live edge eidx[i] of the
-// staged graph. The tail enqueues init, kk x (argmin, argmin, round) and the gather without a synchronisation. pruned /
+// staged graph. The tail enqueues init, kk x (argmin, pick, round) and the gather without a synchronisation. pruned /
 // cond_loss / kld: kk entries (the tail beyond *npruned is -1 / NaN), final_loss / final_margin / status: n each, may be
 // nullptr. Host arrays throughout.
 int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
@@ -3253,20 +2912,9 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     const int D = in.D, DD = D * D;
     const int np = std::min((n + 255) / 256, 256);
     const int look = lazy ? greedy_lookahead(lazy->lookahead, D) : 0;
-    const double own_bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
+    const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
     int rc = 0;
-    if (lazy) {
-        if ((rc = greedy_lazy_capacity("edge pruning", own_bytes, joint_len, D, lazy->m, err, errlen))) return rc;
-    } else {
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
-        if (bytes + (double)(1ull << 30) > (double)free_b) {
-            snprintf(err, errlen, "edge pruning needs %.1f GB for the joint covariance of the endpoints and the histories, %.1f GB are free",
-                     bytes * 1e-9, free_b * 1e-9);
-            return SPG_ECAPACITY;
-        }
-    }
+    if ((rc = greedy_capacity("edge pruning", bytes, joint_len, D, lazy, err, errlen))) return rc;
     DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus, dpslot;
     if ((rc = upload(deidx, eidx, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) || (rc = upload(dsb, sb, (size_t)n, s)) ||
         (lazy && (rc = upload(dpslot, lazy->pslot, (size_t)n, s)))) {
@@ -3301,6 +2949,25 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     hipError_t tail_err = hipSuccess;
     PruneArgs a{};
     LazyArgs z{};
+    // the launches of the call, on s (the stream tail and post are handed), once tail has filled a and z
+    const dim3 per_cand((unsigned)((n + 3) / 4)), wg(256);
+    const auto init = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_prune_init_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        });
+    };
+    const auto stage1 = [&] { hipLaunchKernelGGL(sp_prune_argmin_kernel, dim3((unsigned)np), wg, 0, s, a); };
+    const auto stage2 = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_prune_pick_kernel<decltype(d)::value, decltype(lz)::value>), dim3(1), wg, 0, s, a, z);
+        });
+    };
+    const auto round = [&] {
+        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+            hipLaunchKernelGGL((sp_prune_round_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        });
+    };
+    const auto gather = [&] { hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), wg, 0, s, a); };
     const CovTail tail = [&](hipStream_t st, const GraphBufs &gb, const double *joint) {
         a.arena = gb.dev.arena; a.vpo = gb.dev.vpo; a.er = gb.dev.er; a.ev = gb.dev.ev;
         a.eidx = (const int32_t *)deidx.p; a.sa = (const int32_t *)dsa.p; a.sb = (const int32_t *)dsb.p;
@@ -3311,37 +2978,20 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
         a.sel = (int32_t *)dsel.p; a.cl = (double *)dcl.p; a.ck = (double *)dck.p;
         a.final_loss = (double *)dfl.p; a.final_margin = (double *)dfm.p; a.status = (int32_t *)dstatus.p;
         a.n = n; a.kk = kk; a.np = np; a.max_loss = max_loss; a.max_kld = max_kld; a.min_margin = min_margin;
-        const dim3 per_cand((unsigned)((n + 3) / 4));
-        tail_err = t_prune.start(st);
         if (lazy) {   // round 0 from the pair blocks; the rounds follow in `post`, on the factor
             a.joint = nullptr; a.ld = 0;
             z.blocks = joint; z.pslot = (const int32_t *)dpslot.p; z.rank = (int32_t *)dctl.p + 4; z.L = look; z.ca = z.cb = -1;
-            by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_prune_init_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); });
-            return;
         }
-        by_dim(D, [&](auto d) {
-            constexpr int DV = decltype(d)::value;
-            hipLaunchKernelGGL((sp_prune_init_kernel<DV>), per_cand, dim3(256), 0, st, a);
-            for (int t = 0; t < kk; t++) {
-                hipLaunchKernelGGL((sp_prune_argmin_kernel<DV>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
-                hipLaunchKernelGGL((sp_prune_argmin_kernel<DV>), dim3(1), dim3(256), 0, st, a, 1);
-                hipLaunchKernelGGL((sp_prune_round_kernel<DV>), per_cand, dim3(256), 0, st, a);
-            }
-        });
-        hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+        tail_err = t_prune.start(st);
+        init();
+        if (lazy) return;
+        for (int t = 0; t < kk; t++) { stage1(); stage2(); round(); }
+        gather();
         if (tail_err == hipSuccess) tail_err = t_prune.stop(st);
     };
     const CovPost post = [&](hipStream_t st, SparseSolver &sp, const GraphBufs &gb, int *bad, const std::vector<int32_t> &pos) -> int {
-        const dim3 per_cand((unsigned)((n + 3) / 4));
         return greedy_lazy_rounds(st, sp, gb, bad, pos, *lazy, look, sa, sb, kk, (int32_t *)dctl.p, z, t_prune, stats.solve, err, errlen,
-            [&] {
-                by_dim(D, [&](auto d) {
-                    hipLaunchKernelGGL((sp_prune_argmin_kernel<decltype(d)::value>), dim3((unsigned)np), dim3(256), 0, st, a, 0);
-                    hipLaunchKernelGGL((sp_prune_rank_kernel<decltype(d)::value>), dim3(1), dim3(256), 0, st, a, z);
-                });
-            },
-            [&] { by_dim(D, [&](auto d) { hipLaunchKernelGGL((sp_prune_round_lazy_kernel<decltype(d)::value>), per_cand, dim3(256), 0, st, a, z); }); },
-            [&] { hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a); });
+                                  [&] { stage1(); stage2(); }, round, gather);
     };
     if ((rc = cov_solve_device(s, in, va, vb, dst, ld, nblk, joint_len, djoint, stats.solve, err, errlen, &tail, lazy ? &post : nullptr))) return rc;
     HIPCHK(tail_err);

@@ -1,5 +1,6 @@
 """Greedy selection of loop-closure candidates by conditional information gain (spg_graph_select_candidates,
-csrc/spg_sparse.inc: sp_select_init_kernel / _argmax_kernel / _round_kernel) against the numpy rule of tests/select_ref.py.
+csrc/spg_sparse.inc: sp_select_init_kernel / _argmax_kernel / _pick_kernel / _round_kernel) against the numpy rule of
+tests/select_ref.py.
 CPU: the candidate-space recurrence equals the rule on the dense information (slogdet), the GPU fixtures are decidable,
 the argument contract on an injected backend, the ABI and the bindings, the C++ demo compiles.
 GPU: sequence and gains on small graphs (before and after marginalisation, both gauges), the log det identity through

@@ -1,6 +1,6 @@
 """Greedy edge pruning by conditional information loss and its exact KLD (spg_graph_prune_candidates /
-spg_graph_remove_edges, csrc/spg_sparse.inc: sp_prune_init_kernel / _argmin_kernel / _round_kernel) against the numpy rule
-of tests/prune_ref.py.
+spg_graph_remove_edges, csrc/spg_sparse.inc: sp_prune_init_kernel / _argmin_kernel / _pick_kernel / _round_kernel) against
+the numpy rule of tests/prune_ref.py.
 CPU: the candidate-space recurrence equals the rule on the dense information (slogdet) and the Woodbury form, the KLD
 closed form, dynamic eligibility on a 4-cycle, the GPU lists are decidable, the argument contract and removeEdges on an
 injected backend, the ABI and the bindings, the C++ demo compiles.
