@@ -543,7 +543,52 @@ int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ed
                                double max_loss, double max_kld, double min_margin,
                                int32_t *pruned, double *cond_loss, double *kld, int cap,
                                double *final_loss, double *final_margin, int32_t *status, spg_prune_stats *stats);
-/* ---- how the two greedy calls above get at Sigma ------------------------------------------------------------
+
+/* ---- outlier edges by greedy data snooping -------------------------------------------------------------------
+ * Which of the graph's own binary edges are wrong: the classical normalised-residual test, each edge's leave-one-out
+ * chi^2 statistic, taken greedily and re-conditioned after every rejection. A candidate is a live binary edge, named by
+ * its index in the order of spg_graph_get_edges; J_i, L_i (Omega_i = L_i L_i^T), Sigma (gauge of fixed_id) and C_ij(0)
+ * are those of the pruning above, and e_i(0) is the edge's error at the stored estimates. The stored estimates are TAKEN
+ * AS the minimiser of the linearised problem: call spg_graph_optimize first. The gradient is not checked, and the robust
+ * kernel is ignored. Rounds t = 0, 1, ... run on the device:
+ *   M_i(t)    = I - L_i^T C_ii(t) L_i = G G^T            margin_i = the smallest squared pivot (as the pruning)
+ *   stat_i(t) = |G^-1 L_i^T e_i(t)|^2                     = e_i^T (Omega_i^-1 - C_ii(t))^-1 e_i
+ *   i*        = argmax over the eligible candidates, ties to the lowest index
+ *   K = L* G^-T,  w = K^T e*(t)  (stat* = |w|^2),  B_i,t = C_i*(t) K
+ *   C_ii(t+1) = C_ii(t) + B_i,t B_i,t^T,   e_i(t+1) = e_i(t) + B_i,t w
+ * stat_i(t) is chi^2 with D degrees of freedom for an inlier, and equals the drop of the linearised graph's minimum chi^2
+ * when the edge is left out and the rest is refitted. Eligible is re-evaluated every round exactly as the pruning does:
+ * not yet flagged, Omega finite and positive definite, the factorisation completes and margin >= min_margin (<= 0: the
+ * default 1e-6). Detection stops after k rounds, when nothing is eligible, or when the best statistic is < min_stat
+ * (<= 0: no threshold).
+ * Identities: sum_t stat*(t) = chi^2(0) - chi^2 of the linear refit without the flagged edges. redundancy_i = tr M_i(0)
+ * = D - tr(L_i^T C_ii(0) L_i) lies in [0, D]; over all edges of a graph with binary edges only the redundancies sum to
+ * D (E - V + 1).
+ * NOT DECIDABLE: an edge at a vertex that has exactly two edges has the same statistic as that vertex's other edge (the
+ * vertex absorbs either residual equally); which of the two is wrong cannot be told, and the tie goes to the lower index.
+ * Memory, SPG_ECAPACITY, the greedy method, the argument errors and SPG_ESTATE exactly as spg_graph_prune_candidates
+ * (the per-candidate state grows by the D doubles of e_i; the statistic takes the place of the loss). The graph is NOT modified: apply a result with
+ * spg_graph_remove_edges. */
+enum { SPG_OUTLIER_INLIER = 0, SPG_OUTLIER_INFO_NOT_PD = 1, SPG_OUTLIER_UNTESTABLE = 2, SPG_OUTLIER_FLAGGED = 3 };
+typedef struct {
+    spg_cov_solve_stats solve;   /* the covariance part; its device_seconds covers the detection too */
+    int32_t rounds;              /* rounds run = edges flagged */
+    int32_t endpoints;           /* m */
+    double detect_seconds;       /* HIP-event time of the detection alone: initial statistics, the rounds, final values */
+} spg_outlier_stats;
+/* flagged, stat: min(k, n) entries in order; flagged[t] indexes edge_idx, stat[t] = its statistic when it was chosen;
+ * entries beyond the return value are -1 / NaN. Per candidate (n each, each may be NULL): final_stat = the statistic after
+ * the last round, NaN unless the status is SPG_OUTLIER_INLIER; final_margin = the margin after the last round, NaN for
+ * flagged and not-PD candidates; redundancy as above (round 0), NaN for not-PD candidates; status = SPG_OUTLIER_*,
+ * _UNTESTABLE meaning ineligible by margin after the last round (a bridge: its residual is zero by construction). Returns
+ * the number flagged; with cap < min(k, n) (or flagged / stat NULL) returns min(k, n) and writes nothing. n = 0 or k = 0
+ * returns 0. */
+int spg_graph_detect_outliers(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k,
+                              double min_stat, double min_margin,
+                              int32_t *flagged, double *stat, int cap,
+                              double *final_stat, double *final_margin, double *redundancy, int32_t *status,
+                              spg_outlier_stats *stats);
+/* ---- how the greedy calls above get at Sigma ------------------------------------------------------------
  * SPG_GREEDY_JOINT (default): the m D x m D joint block described above, and its 46 000 bound.
  * SPG_GREEDY_LAZY: no joint block, and no bound on m D. Round 0 comes from one 2D x 2D block per distinct ordered endpoint
  *   pair (the blocks of spg_graph_relative_covariances: every prune candidate is an edge, so its block is read from the
@@ -572,7 +617,7 @@ typedef struct {
     double round_solve_seconds;      /* HIP-event time of the per-round sweeps */
     double cache_bytes;              /* size of the column cache */
 } spg_greedy_stats;
-/* of the context's last spg_graph_select_candidates / _prune_candidates call that reached the device (all zero before) */
+/* of the context's last spg_graph_select_candidates / _prune_candidates / _detect_outliers call that reached the device (all zero before) */
 int spg_ctx_greedy_stats(spg_ctx *ctx, spg_greedy_stats *out);
 
 /* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is

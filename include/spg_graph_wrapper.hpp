@@ -638,6 +638,41 @@ public:
         removeEdges(gone);
         return out;
     }
+    // Greedy data snooping over the listed live binary edges (include/spg.h: spg_graph_detect_outliers): each round flags
+    // the edge with the largest leave-one-out chi^2 statistic given the ones already flagged; the graph is not modified.
+    // Call optimize() first: the stored estimates are taken as the minimiser. min_stat <= 0: no threshold.
+    struct OutlierResult {
+        std::vector<int> flagged;         // indices into edge_idx, in order
+        std::vector<double> stat;         // the statistic of flagged[t] when it was chosen
+        std::vector<double> final_stat, final_margin, redundancy;   // per candidate
+        std::vector<int> status;          // SPG_OUTLIER_* per candidate
+    };
+    OutlierResult detectOutliers(const std::vector<int> &edge_idx, int k, double min_stat = 0.0, double min_margin = 0.0, int fixed_id = -1,
+                                 spg_outlier_stats *stats = nullptr) {
+        const int n = (int)edge_idx.size(), cap = std::max(std::min(k, n), 0);
+        std::vector<int32_t> idx(edge_idx.begin(), edge_idx.end()), sel((size_t)std::max(cap, 1)), st((size_t)std::max(n, 1));
+        std::vector<double> cs(sel.size()), fs(st.size()), fm(st.size()), red(st.size());
+        const int r = spg_graph_detect_outliers(_g, fixed_id, idx.data(), n, k, min_stat, min_margin, sel.data(), cs.data(), cap, fs.data(), fm.data(),
+                                                red.data(), st.data(), stats);
+        check(std::min(r, 0), "detectOutliers");
+        OutlierResult out;
+        out.flagged.assign(sel.begin(), sel.begin() + r);
+        out.stat.assign(cs.begin(), cs.begin() + r);
+        out.final_stat.assign(fs.begin(), fs.begin() + n);
+        out.final_margin.assign(fm.begin(), fm.begin() + n);
+        out.redundancy.assign(red.begin(), red.begin() + n);
+        out.status.assign(st.begin(), st.begin() + n);
+        return out;
+    }
+    // detectOutliers followed by removeEdges of what it flagged
+    OutlierResult rejectOutliers(const std::vector<int> &edge_idx, int k, double min_stat = 0.0, double min_margin = 0.0, int fixed_id = -1,
+                                 spg_outlier_stats *stats = nullptr) {
+        OutlierResult out = detectOutliers(edge_idx, k, min_stat, min_margin, fixed_id, stats);
+        std::vector<int> gone;
+        for (int t : out.flagged) gone.push_back(edge_idx[(size_t)t]);
+        removeEdges(gone);
+        return out;
+    }
     // called on the baseline: kullbackLeiblerDivergence (src/utils.cpp:70-97) of each vertex's marginal in `other` against
     // its marginal here, every vertex of `other` but the fixed one; ids ascending
     std::vector<double> marginalKullbackLeibler(GraphWrapper *other, std::vector<int> *ids = nullptr, int fixed_id = -1, spg_cov_stats *stats = nullptr) {

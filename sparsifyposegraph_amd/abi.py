@@ -132,7 +132,21 @@ class PruneStats(C.Structure):
         return d
 
 
-# SPG_GREEDY_* (include/spg.h): how spg_graph_select_candidates / _prune_candidates get at Sigma, spg_ctx_set_greedy_method
+# SPG_OUTLIER_* (include/spg.h): status of a candidate of spg_graph_detect_outliers
+OUTLIER_INLIER, OUTLIER_INFO_NOT_PD, OUTLIER_UNTESTABLE, OUTLIER_FLAGGED = 0, 1, 2, 3
+
+
+class OutlierStats(C.Structure):
+    """spg_outlier_stats (include/spg.h)"""
+    _fields_ = [("solve", CovSolveStats), ("rounds", C.c_int32), ("endpoints", C.c_int32), ("detect_seconds", C.c_double)]
+
+    def asdict(self):
+        d = self.solve.asdict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_[1:]})
+        return d
+
+
+# SPG_GREEDY_* (include/spg.h): how spg_graph_select_candidates / _prune_candidates / _detect_outliers get at Sigma, spg_ctx_set_greedy_method
 GREEDY_JOINT, GREEDY_LAZY, GREEDY_AUTO = 0, 1, 2
 
 

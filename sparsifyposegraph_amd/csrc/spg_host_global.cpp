@@ -641,13 +641,18 @@ extern "C" int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const
     return select_call(g, fixed_id, ij, records, n, k, min_gain, max_d2, selected, cond_gain, cap, final_gain, status, stats);
 }
 
-// ================================================================================= greedy edge pruning
-// spg_graph_prune_candidates: candidate i is live edge edge_idx[i] in the order of spg_graph_get_edges, which is the order
-// of the staged edge list; the endpoint set, its joint covariance and the slots are built as in select_call.
-extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k, double max_loss, double max_kld,
-                                          double min_margin, int32_t *pruned, double *cond_loss, double *kld, int cap, double *final_loss,
-                                          double *final_margin, int32_t *status, spg_prune_stats *stats) {
-    const char *what = "spg_graph_prune_candidates";
+// ================================================================================= greedy edge pruning, outlier detection
+namespace {
+// What spg_graph_prune_candidates and spg_graph_detect_outliers share. Candidate i is live edge edge_idx[i] in the order
+// of spg_graph_get_edges, which is the order of the staged edge list; the endpoint set, its joint covariance and the slots
+// are built as in select_call. `outputs`: the caller's ordered arrays are there (else the size query). run(in, va, vb,
+// dst, ld, nblk, len, sa, sb, kk, m, lazy) is the device call: it resets its stats for m endpoints and writes the number
+// chosen to `count`. `ran` is set when a device call succeeded: the return value is then `count`, and the caller's stats
+// are those of the result (a size query, n = 0 or k = 0 and every error leave it false).
+template <class Run>
+int edge_greedy_call(spg_graph *g, const char *what, int32_t fixed_id, const int32_t *edge_idx, int n, int k, bool outputs, int cap, const int &count,
+                     bool &ran, Run run) {
+    ran = false;
     if (!g || n < 0 || (n > 0 && !edge_idx)) return SPG_EINVAL;
     if (k < 0) return set_err(g->ctx, SPG_EINVAL, "%s: k is negative", what);
     if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
@@ -689,11 +694,7 @@ extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const 
                  what, (long long)m);
         return SPG_ECAPACITY;
     }
-    if (!pruned || !cond_loss || !kld || cap < kk) return kk;
-    spg_prune_stats ps{};
-    ps.endpoints = (int32_t)m;
-    int npruned = 0;
-    const double margin = min_margin > 0.0 ? min_margin : 1e-6;
+    if (!outputs || cap < kk) return kk;
     if (method == SPG_GREEDY_JOINT || (method == SPG_GREEDY_AUTO && W <= 46000)) {
         std::vector<int32_t> va, vb;
         std::vector<int64_t> dst;
@@ -703,17 +704,14 @@ extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const 
         DenseStage st;
         const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
         if (staged < 0) return staged;
-        const int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
-                                             edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, margin, pruned, cond_loss, kld, final_loss,
-                                             final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err);
+        const int rc = run(st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need, sa.data(), sb.data(), kk, (int32_t)m,
+                           (const spg::GreedyLazyIn *)nullptr);
         if (rc == 0) {
-            joint_greedy_stats(g->ctx, ps.rounds);
-            if (stats) *stats = ps;
-            return npruned;
+            joint_greedy_stats(g->ctx, count);
+            ran = true;
+            return count;
         }
         if (!(method == SPG_GREEDY_AUTO && rc == SPG_ECAPACITY)) return rc;   // AUTO: what JOINT cannot hold goes to LAZY
-        ps = spg_prune_stats{};
-        ps.endpoints = (int32_t)m;
     }
     PairBlocks pb;   // every pair is an edge: its block lies in the fronts of the selected inverse
     for (int i = 0; i < n; i++) { const GEdge &ge = g->edges[live[edge_idx[i]]]; pb.add(ge.vtx[0], ge.vtx[1], D); }
@@ -721,11 +719,51 @@ extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const 
     const int staged = cov_stage(g, fixed, order, {&pb.va, &pb.vb}, pb.len(D), nullptr, what, st);
     if (staged < 0) return staged;
     const spg::GreedyLazyIn lz{pb.slot.data(), S.data(), (int)m, g->ctx->greedy_lookahead, &g->ctx->greedy_stats};
-    if (int rc = spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), st.in, pb.va.data(), pb.vb.data(), pb.dst.data(), (int32_t)(2 * D),
-                                       (int64_t)pb.va.size(), pb.len(D), edge_idx, sa.data(), sb.data(), n, kk, max_loss, max_kld, margin, pruned, cond_loss,
-                                       kld, final_loss, final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err, &lz)) return rc;
-    if (stats) *stats = ps;
-    return npruned;
+    if (int rc = run(st.in, pb.va.data(), pb.vb.data(), pb.dst.data(), (int32_t)(2 * D), (int64_t)pb.va.size(), pb.len(D), sa.data(), sb.data(), kk,
+                     (int32_t)m, &lz)) return rc;
+    ran = true;
+    return count;
+}
+}  // namespace
+
+extern "C" int spg_graph_prune_candidates(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k, double max_loss, double max_kld,
+                                          double min_margin, int32_t *pruned, double *cond_loss, double *kld, int cap, double *final_loss,
+                                          double *final_margin, int32_t *status, spg_prune_stats *stats) {
+    spg_prune_stats ps{};
+    int npruned = 0;
+    bool ran = false;
+    const double margin = min_margin > 0.0 ? min_margin : 1e-6;
+    const int r = edge_greedy_call(
+        g, "spg_graph_prune_candidates", fixed_id, edge_idx, n, k, pruned && cond_loss && kld, cap, npruned, ran,
+        [&](const spg::DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk, int64_t len, const int32_t *sa,
+            const int32_t *sb, int kk, int32_t m, const spg::GreedyLazyIn *lz) {
+            ps = spg_prune_stats{};
+            ps.endpoints = m;
+            return spg::hip_sparse_prune(spg::hip_backend_stream(&g->ctx->be), in, va, vb, dst, ld, nblk, len, edge_idx, sa, sb, n, kk, max_loss, max_kld,
+                                         margin, pruned, cond_loss, kld, final_loss, final_margin, status, &npruned, ps, g->ctx->err, sizeof g->ctx->err, lz);
+        });
+    if (ran && stats) *stats = ps;
+    return r;
+}
+
+extern "C" int spg_graph_detect_outliers(spg_graph *g, int32_t fixed_id, const int32_t *edge_idx, int n, int k, double min_stat, double min_margin,
+                                         int32_t *flagged, double *stat, int cap, double *final_stat, double *final_margin, double *redundancy,
+                                         int32_t *status, spg_outlier_stats *stats) {
+    spg_outlier_stats os{};
+    int nflagged = 0;
+    bool ran = false;
+    const double margin = min_margin > 0.0 ? min_margin : 1e-6;
+    const int r = edge_greedy_call(
+        g, "spg_graph_detect_outliers", fixed_id, edge_idx, n, k, flagged && stat, cap, nflagged, ran,
+        [&](const spg::DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk, int64_t len, const int32_t *sa,
+            const int32_t *sb, int kk, int32_t m, const spg::GreedyLazyIn *lz) {
+            os = spg_outlier_stats{};
+            os.endpoints = m;
+            return spg::hip_sparse_detect(spg::hip_backend_stream(&g->ctx->be), in, va, vb, dst, ld, nblk, len, edge_idx, sa, sb, n, kk, min_stat, margin,
+                                          flagged, stat, final_stat, final_margin, redundancy, status, &nflagged, os, g->ctx->err, sizeof g->ctx->err, lz);
+        });
+    if (ran && stats) *stats = os;
+    return r;
 }
 
 // ================================================================================= robust kernel

@@ -152,6 +152,12 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
                      int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
                      double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
                      int *npruned, spg_prune_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy = nullptr);
+// Greedy data snooping (the same kernels with the statistic as the objective). Arguments as hip_sparse_prune.
+// flagged, stat: kk entries; final_stat, final_margin, redundancy, status: n each, may be nullptr.
+int hip_sparse_detect(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                      int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double min_stat, double min_margin,
+                      int32_t *flagged, double *stat, double *final_stat, double *final_margin, double *redundancy, int32_t *status, int *nflagged,
+                      spg_outlier_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy = nullptr);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

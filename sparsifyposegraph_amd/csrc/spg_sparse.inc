@@ -1122,6 +1122,12 @@ __global__ __launch_bounds__(256) void sp_select_gather_kernel(SelArgs a) {
 // argmin of loss_i = -1/2 ln det M_i, M_i = I - L_i^T C_ii L_i = G G^T, over the candidates in state 0 whose smallest
 // squared pivot (the margin) is >= min_margin, and conditions on its removal: B_i,t = C_i*(t) L* G^-T with C_i*(t) =
 // C_i*(0) + sum_{s<t} B_i,s B_*,s^T, C_ii += B_i,t B_i,t^T. States: 0 live, 1 Omega not PD, 3 pruned.
+// The same kernels, instantiated with OBJ_STAT, are the greedy data snooping of spg_graph_detect_outliers (DESIGN 5g-O):
+// the objective is stat_i = |G^-1 L_i^T e_i|^2 instead of the loss (kept in `loss`), i* is its argmax, the stop rule is
+// min_stat, and a round also moves the residuals, e_i += B_i,t w with w = G^-1 L*^T e*. Everything that differs sits
+// under `if constexpr (OBJ == OBJ_STAT)`. The two fields only one objective reads share their place with the other's, so
+// that the argument block, and with it the code of the OBJ_LOSS instantiations, is what it was before OBJ existed.
+enum { OBJ_LOSS = 0, OBJ_STAT = 1 };
 struct PruneArgs {
     const double *arena;
     const int64_t *vpo;
@@ -1139,13 +1145,20 @@ struct PruneArgs {
     int32_t *pi;
     int32_t *ctl;             // [0] rounds done = number pruned, [1] a stop rule has fired, [2] i* of the current round
     double *pubC;             // D^2: C_**(t) as it was when i* was picked
-    double *kldsum;           // one double: the cumulative KLD (written by thread 0 of argmin stage 2 alone)
+    union {
+        double *kldsum;       // OBJ_LOSS: one double, the cumulative KLD (written by thread 0 of argmin stage 2 alone)
+        double *e;            // OBJ_STAT: n x D, e_i(t); pubC is then D^2 + D long, e* behind C**
+    };
     int32_t *sel;             // kk: the choices in order
     double *cl, *ck;          // kk: their conditional losses, the cumulative KLD after each
     double *final_loss, *final_margin;   // n each
     int32_t *status;          // n: SPG_PRUNE_*
     int n, kk, np;
-    double max_loss, max_kld, min_margin;
+    union {
+        double max_loss;      // OBJ_LOSS
+        double min_stat;      // OBJ_STAT
+    };
+    double max_kld, min_margin;
 };
 // lanes < D^2: M = I - L^T A, r <= c, mirrored
 template <int D>
@@ -1184,9 +1197,28 @@ __device__ __forceinline__ bool rel_chol_downdate(double *M, double min_margin, 
     margin_out = margin;
     return ok;
 }
+// lane 0: y = L^T e (L lower triangular), then G x = y in place (G: the lower triangle of M); returns |x|^2
+template <int D>
+__device__ __forceinline__ double rel_whiten_solve(const double *L, const double *e, const double *G, double *y) {
+    for (int c = 0; c < D; c++) {
+        double s = 0;
+        for (int r = c; r < D; r++) s += L[r * D + c] * e[r];
+        y[c] = s;
+    }
+    double n2 = 0;
+    for (int j = 0; j < D; j++) {
+        double x = y[j];
+        for (int k = 0; k < j; k++) x -= G[j * D + k] * y[k];
+        x /= G[j * D + j];
+        y[j] = x;
+        n2 += x * x;
+    }
+    return n2;
+}
 // One wavefront per candidate, four per workgroup, the LDS slice of sp_select_init_kernel: J, L, C_ii(0) = P, tr0, the
-// loss and the margin of round 0, and the state (Omega not finite or not PD: 1, else 0). Sigma: as there.
-template <int D, bool LAZY>
+// loss (OBJ_STAT: the statistic, and e_i(0)) and the margin of round 0, and the state (Omega not finite or not PD: 1,
+// else 0). Sigma: as there.
+template <int D, bool LAZY, int OBJ>
 __global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D, PS = (D == 6) ? 7 : 3;
     constexpr int PER = W * W + 2 * DD + D * W + 2 * DD + 2 * D;
@@ -1229,8 +1261,14 @@ __global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a, LazyArg
     __syncthreads();
     if (act && lane == 0) {
         double loss = __builtin_nan(""), margin = loss;
-        if (go) rel_chol_downdate<D>(M, a.min_margin, loss, margin);
-        else a.tr0[i] = loss;
+        if (go) {
+            const bool ok = rel_chol_downdate<D>(M, a.min_margin, loss, margin);
+            if constexpr (OBJ == OBJ_STAT) {
+                if (ok) loss = rel_whiten_solve<D>(L, e, M, y);
+            }
+        } else {
+            a.tr0[i] = loss;
+        }
         a.loss[i] = loss;
         a.margin[i] = margin;
         a.state[i] = go ? 0 : 1;
@@ -1241,45 +1279,72 @@ __global__ __launch_bounds__(256) void sp_prune_init_kernel(PruneArgs a, LazyArg
         a.L[(long long)i * DD + lane] = L[lane];
         a.C[(long long)i * DD + lane] = P[lane];
     }
+    if constexpr (OBJ == OBJ_STAT) {
+        if (act && lane < D) a.e[(long long)i * D + lane] = e[lane];   // written by lane 0 three barriers ago
+    }
 }
 // (loss ascending, index ascending): the order of the argmin, independent of the grid
 __device__ __forceinline__ bool prn_better(double ga, int ia, double gb, int ib) { return ga < gb || (ga == gb && ia < ib); }
+// (statistic descending, index ascending): the order of the outlier argmax
+__device__ __forceinline__ bool out_better(double ga, int ia, double gb, int ib) { return ga > gb || (ga == gb && ia < ib); }
+// the order of an objective, and the value every candidate beats
+template <int OBJ>
+__device__ __forceinline__ bool obj_better(double ga, int ia, double gb, int ib) {
+    if constexpr (OBJ == OBJ_STAT) return out_better(ga, ia, gb, ib);
+    else return prn_better(ga, ia, gb, ib);
+}
+template <int OBJ>
+__device__ __forceinline__ double obj_worst() { return OBJ == OBJ_STAT ? -__builtin_inf() : __builtin_inf(); }
 // Stage 1 of the argmin (np workgroups): the best (loss, index) per workgroup of the candidates in state 0 that are
 // eligible this round (a loss that is not NaN, margin >= min_margin; the others stay in state 0) into pg / pi.
+template <int OBJ>
 __global__ __launch_bounds__(256) void sp_prune_argmin_kernel(PruneArgs a) {
     __shared__ double sg[256];
     __shared__ int si[256];
     const int stop = a.ctl[1];   // nothing in this kernel writes ctl
-    double g = __builtin_inf();
+    double g = obj_worst<OBJ>();
     int bi = 0x7fffffff;
     if (!stop)
         for (int i = blockIdx.x * 256 + threadIdx.x; i < a.n; i += gridDim.x * 256) {
             const double l = a.loss[i];
-            if (a.state[i] == 0 && l == l && a.margin[i] >= a.min_margin && prn_better(l, i, g, bi)) { g = l; bi = i; }
+            if (a.state[i] == 0 && l == l && a.margin[i] >= a.min_margin && obj_better<OBJ>(l, i, g, bi)) { g = l; bi = i; }
         }
-    best_reduce<prn_better>(g, bi, sg, si);
+    best_reduce<obj_better<OBJ>>(g, bi, sg, si);
     if (!stop && threadIdx.x == 0) { a.pg[blockIdx.x] = g; a.pi[blockIdx.x] = bi; }
 }
 // Stage 2 (one workgroup): the best of the partials; none, a loss above max_loss or a cumulative KLD above max_kld:
 // ctl[1] = 1. Else i* is appended to sel / cl / ck, marked pruned, and its C_ii is published for the round kernel. RANK
-// (the lazy rounds) adds the ranked list over the candidates eligible this round, in the order of prn_better.
-template <int D, bool RANK>
+// (the lazy rounds) adds the ranked list over the candidates eligible this round, in the order of the objective.
+// OBJ_STAT: the one stop rule is a best statistic below min_stat, there is no KLD, and e* is published behind C**.
+template <int D, bool RANK, int OBJ>
 __global__ __launch_bounds__(256) void sp_prune_pick_kernel(PruneArgs a, LazyArgs z) {
     constexpr int DD = D * D;
     __shared__ double sg[256];
     __shared__ int si[256];
     __shared__ int chosen;
     const int stop = a.ctl[1];   // read by every thread before the first barrier; written after it by thread 0 alone
-    double g = __builtin_inf();
+    double g = obj_worst<OBJ>();
     int bi = 0x7fffffff;
     if (!stop)
         for (int p = threadIdx.x; p < a.np; p += 256)
-            if (prn_better(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
-    best_reduce<prn_better>(g, bi, sg, si);
+            if (obj_better<OBJ>(a.pg[p], a.pi[p], g, bi)) { g = a.pg[p]; bi = a.pi[p]; }
+    best_reduce<obj_better<OBJ>>(g, bi, sg, si);
     if (stop) return;
     if (threadIdx.x == 0) {
         chosen = -1;
-        if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
+        if constexpr (OBJ == OBJ_STAT) {
+            if (bi == 0x7fffffff || (a.min_stat > 0.0 && g < a.min_stat)) {
+                a.ctl[1] = 1;
+            } else {
+                const int c = a.ctl[0];
+                a.sel[c] = bi;
+                a.cl[c] = g;
+                a.ctl[0] = c + 1;
+                a.ctl[2] = bi;
+                a.state[bi] = 3;
+                chosen = bi;
+            }
+        } else if (bi == 0x7fffffff || (a.max_loss > 0.0 && g > a.max_loss)) {
             a.ctl[1] = 1;
         } else {
             const double kld = a.kldsum[0] + (g - 0.5 * a.tr0[bi]);
@@ -1302,20 +1367,23 @@ __global__ __launch_bounds__(256) void sp_prune_pick_kernel(PruneArgs a, LazyArg
     __syncthreads();
     const int ch = chosen;
     if (ch >= 0 && threadIdx.x < DD) a.pubC[threadIdx.x] = a.C[(long long)ch * DD + threadIdx.x];
+    if constexpr (OBJ == OBJ_STAT) {
+        if (ch >= 0 && threadIdx.x < D) a.pubC[DD + threadIdx.x] = a.e[(long long)ch * D + threadIdx.x];
+    }
     if constexpr (RANK) {
         double pg = g;
         int pi = ch >= 0 ? bi : 0x7fffffff;
         for (int r = 1; r < z.L; r++) {
-            double ng = __builtin_inf();
+            double ng = obj_worst<OBJ>();
             int ni = 0x7fffffff;
             if (pi != 0x7fffffff)
                 for (int i = threadIdx.x; i < a.n; i += 256) {
                     const double l = a.loss[i];
                     if (a.state[i] != 0 || !(l == l) || !(a.margin[i] >= a.min_margin)) continue;
-                    if (prn_better(pg, pi, l, i) && prn_better(l, i, ng, ni)) { ng = l; ni = i; }
+                    if (obj_better<OBJ>(pg, pi, l, i) && obj_better<OBJ>(l, i, ng, ni)) { ng = l; ni = i; }
                 }
             __syncthreads();   // every thread has read sg[0] / si[0] of the previous reduction
-            best_reduce<prn_better>(ng, ni, sg, si);
+            best_reduce<obj_better<OBJ>>(ng, ni, sg, si);
             if (threadIdx.x == 0) z.rank[r] = ni == 0x7fffffff ? -1 : ni;
             pg = ng; pi = ni;
         }
@@ -1324,11 +1392,12 @@ __global__ __launch_bounds__(256) void sp_prune_pick_kernel(PruneArgs a, LazyArg
 // Conditions every candidate still in state 0, and i* itself, on the removal of i* (read from ctl), then re-evaluates the
 // candidate's own M, loss and margin. One wavefront per candidate. M of i* passed the margin test when it was picked; if
 // its factorisation fails all the same, the candidate gets a NaN loss and margin and nothing else of it is touched.
-// Sigma: as in sp_select_round_kernel.
-template <int D, bool LAZY>
+// Sigma: as in sp_select_round_kernel. OBJ_STAT: the slice grows by e*, w = G^-1 L*^T e*, e_i and the solve's vector
+// (4 D doubles: 678 per wavefront at D = 6, 21.7 KB per workgroup); e_i += B_i,t w, and the objective is the statistic.
+template <int D, bool LAZY, int OBJ>
 __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyArgs z) {
     constexpr int W = 2 * D, DD = D * D;
-    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D;
+    constexpr int PER = W * W + 4 * DD + D * W + 8 * DD + D + (OBJ == OBJ_STAT ? 4 * D : 0);
     __shared__ double lds[4 * PER];
     __shared__ int okv[4];
     if (a.ctl[1]) return;   // nothing in this kernel writes ctl
@@ -1337,6 +1406,7 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyAr
     const bool act = i < a.n && (i == s || a.state[i] == 0), go = act && i != s;
     double *S = lds + w * PER, *Ji = S + W * W, *Js = Ji + 2 * DD, *T = Js + 2 * DD, *X = T + D * W, *Ls = X + DD, *Ms = Ls + DD, *As = Ms + DD,
            *K = As + DD, *B = K + DD, *Li = B + DD, *Ci = Li + DD;
+    double *es = Ci + DD + D, *wv = es + D, *ei = wv + D, *yi = ei + D;   // OBJ_STAT only: behind the slice of OBJ_LOSS
     if (act) {
         if constexpr (LAZY) lazy_load_sigma<D>(lane, z.cache, z.strip_len, a.sa[i], a.sb[i], z.ca, z.cb, S);
         else sel_load_sigma<D>(lane, a.joint, a.ld, a.sa[i], a.sb[i], a.sa[s], a.sb[s], S);
@@ -1349,6 +1419,12 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyAr
             Ms[lane] = a.pubC[lane];
             Li[lane] = a.L[(long long)i * DD + lane];
             Ci[lane] = a.C[(long long)i * DD + lane];
+        }
+        if constexpr (OBJ == OBJ_STAT) {
+            if (lane < D) {
+                es[lane] = a.pubC[DD + lane];
+                ei[lane] = a.e[(long long)i * D + lane];
+            }
         }
     }
     __syncthreads();
@@ -1376,6 +1452,9 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyAr
         double l, m;
         okv[w] = rel_chol_downdate<D>(Ms, 0.0, l, m);  // G in the lower triangle of Ms
         if (!okv[w]) { a.loss[i] = __builtin_nan(""); a.margin[i] = __builtin_nan(""); }
+        if constexpr (OBJ == OBJ_STAT) {
+            if (okv[w]) rel_whiten_solve<D>(Ls, es, Ms, wv);   // w = G^-1 L*^T e*
+        }
     }
     __syncthreads();
     const bool upd = act && okv[w];
@@ -1406,6 +1485,14 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyAr
             Ci[c * D + r] = v;
         }
     }
+    if constexpr (OBJ == OBJ_STAT) {
+        if (upd && go && lane < D) {                   // e_i += B_i,t w
+            double v = ei[lane];
+            for (int q = 0; q < D; q++) v += B[lane * D + q] * wv[q];
+            ei[lane] = v;
+            a.e[(long long)i * D + lane] = v;
+        }
+    }
     __syncthreads();
     const bool re = upd && go;
     if (upd && lane < DD) {
@@ -1417,13 +1504,19 @@ __global__ __launch_bounds__(256) void sp_prune_round_kernel(PruneArgs a, LazyAr
     __syncthreads();
     if (re && lane == 0) {
         double l, m;
-        rel_chol_downdate<D>(Ms, a.min_margin, l, m);
+        const bool ok = rel_chol_downdate<D>(Ms, a.min_margin, l, m);
+        if constexpr (OBJ == OBJ_STAT) {
+            if (ok) l = rel_whiten_solve<D>(Li, ei, Ms, yi);
+        } else {
+            (void)ok;
+        }
         a.loss[i] = l;
         a.margin[i] = m;
     }
 }
 // final_loss / final_margin / status after the last round: a candidate still in state 0 is SPG_PRUNE_BRIDGE when its
-// margin is below min_margin or NaN (final_loss NaN), else SPG_PRUNE_KEPT
+// margin is below min_margin or NaN (final_loss NaN), else SPG_PRUNE_KEPT. The SPG_OUTLIER_* values are the same four, and
+// `loss` then holds the statistic.
 __global__ __launch_bounds__(256) void sp_prune_gather_kernel(PruneArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
@@ -2721,6 +2814,14 @@ void by_dim_lazy(int D, bool lazy, F &&f) {
     by_dim(D, [&](auto d) { lazy ? f(d, std::true_type{}) : f(d, std::false_type{}); });
 }
 
+// by_dim_lazy with the objective of the edge kernels (OBJ_LOSS / OBJ_STAT) as a third constant
+template <class F>
+void by_dim_lazy_obj(int D, bool lazy, int obj, F &&f) {
+    by_dim_lazy(D, lazy, [&](auto d, auto lz) {
+        obj == OBJ_STAT ? f(d, lz, std::integral_constant<int, OBJ_STAT>{}) : f(d, lz, std::integral_constant<int, OBJ_LOSS>{});
+    });
+}
+
 // The free-HBM check of a greedy call, before anything is allocated. bytes: the joint block (a lazy call: the pair
 // blocks), blocks_len doubles, plus the histories and the state; a lazy call adds two column strips, and its panel
 // workspace is checked once the plan is known.
@@ -2900,22 +3001,25 @@ int hip_sparse_select(void *stream, const DenseGraphIn &in, const int32_t *va, c
     return 0;
 }
 
-// spg_graph_prune_candidates: the sub-block lists and slots as hip_sparse_select; candidate i is live edge eidx[i] of the
-// staged graph. The tail enqueues init, kk x (argmin, pick, round) and the gather without a synchronisation. pruned /
-// cond_loss / kld: kk entries (the tail beyond *npruned is -1 / NaN), final_loss / final_margin / status: n each, may be
-// nullptr. Host arrays throughout.
-int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
-                     int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
-                     double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
-                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
+// spg_graph_prune_candidates (obj = OBJ_LOSS) and spg_graph_detect_outliers (OBJ_STAT): the sub-block lists and slots as
+// hip_sparse_select; candidate i is live edge eidx[i] of the staged graph. The tail enqueues init, kk x (argmin / argmax,
+// pick, round) and the gather without a synchronisation. chosen / value / kld: kk entries (the tail beyond *nchosen is
+// -1 / NaN; kld: OBJ_LOSS only), final_value / final_margin / status: n each, may be nullptr; redundancy (OBJ_STAT, n,
+// may be nullptr) = D - tr0. limit: max_loss or min_stat. Host arrays throughout.
+struct EdgeGreedyTimes { spg_cov_solve_stats &solve; int32_t &rounds; double &seconds; };
+static int greedy_edges(int obj, const char *what, void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld,
+                        int64_t nblk, int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double limit,
+                        double max_kld, double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin,
+                        double *redundancy, int32_t *status, int *npruned, EdgeGreedyTimes stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
     hipStream_t s = (hipStream_t)stream;
     const int D = in.D, DD = D * D;
+    const bool snoop = obj == OBJ_STAT;
     const int np = std::min((n + 255) / 256, 256);
     const int look = lazy ? greedy_lookahead(lazy->lookahead, D) : 0;
-    const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7));
+    const double bytes = 8.0 * ((double)joint_len + (double)n * kk * DD + (double)n * (4 * DD + 7 + (snoop ? D : 0)));
     int rc = 0;
-    if ((rc = greedy_capacity("edge pruning", bytes, joint_len, D, lazy, err, errlen))) return rc;
-    DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus, dpslot;
+    if ((rc = greedy_capacity(what, bytes, joint_len, D, lazy, err, errlen))) return rc;
+    DevBuf djoint, deidx, dsa, dsb, dJ, dL, dC, dhist, dloss, dmargin, dtr0, dstate, dpg, dpi, dctl, dpub, dksum, dsel, dcl, dck, dfl, dfm, dstatus, dpslot, de;
     if ((rc = upload(deidx, eidx, (size_t)n, s)) || (rc = upload(dsa, sa, (size_t)n, s)) || (rc = upload(dsb, sb, (size_t)n, s)) ||
         (lazy && (rc = upload(dpslot, lazy->pslot, (size_t)n, s)))) {
         snprintf(err, errlen, "staging the candidates failed (%d)", rc);
@@ -2932,19 +3036,20 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     HIPCHK(hipMalloc(&dpg.p, (size_t)np * 8));
     HIPCHK(hipMalloc(&dpi.p, (size_t)np * sizeof(int32_t)));
     HIPCHK(hipMalloc(&dctl.p, kGreedyCtl * sizeof(int32_t)));   // 4 control words, then the lazy form's ranked list
-    HIPCHK(hipMalloc(&dpub.p, (size_t)DD * 8));
-    HIPCHK(hipMalloc(&dksum.p, 8));
+    HIPCHK(hipMalloc(&dpub.p, (size_t)(DD + (snoop ? D : 0)) * 8));
+    if (snoop) HIPCHK(hipMalloc(&de.p, (size_t)n * D * 8));
+    if (!snoop) HIPCHK(hipMalloc(&dksum.p, 8));
     HIPCHK(hipMalloc(&dsel.p, (size_t)kk * sizeof(int32_t)));
     HIPCHK(hipMalloc(&dcl.p, (size_t)kk * 8));
-    HIPCHK(hipMalloc(&dck.p, (size_t)kk * 8));
+    if (!snoop) HIPCHK(hipMalloc(&dck.p, (size_t)kk * 8));   // the statistic has no KLD: cl alone
     HIPCHK(hipMalloc(&dfl.p, (size_t)n * 8));
     HIPCHK(hipMalloc(&dfm.p, (size_t)n * 8));
     HIPCHK(hipMalloc(&dstatus.p, (size_t)n * sizeof(int32_t)));
     HIPCHK(hipMemsetAsync(dctl.p, 0, 4 * sizeof(int32_t), s));
-    HIPCHK(hipMemsetAsync(dksum.p, 0, 8, s));
+    if (!snoop) HIPCHK(hipMemsetAsync(dksum.p, 0, 8, s));
     HIPCHK(hipMemsetAsync(dsel.p, 0xff, (size_t)kk * sizeof(int32_t), s));   // -1
     HIPCHK(hipMemsetAsync(dcl.p, 0xff, (size_t)kk * 8, s));                  // NaN
-    HIPCHK(hipMemsetAsync(dck.p, 0xff, (size_t)kk * 8, s));
+    if (!snoop) HIPCHK(hipMemsetAsync(dck.p, 0xff, (size_t)kk * 8, s));
     EventTimer t_prune;
     hipError_t tail_err = hipSuccess;
     PruneArgs a{};
@@ -2952,19 +3057,22 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     // the launches of the call, on s (the stream tail and post are handed), once tail has filled a and z
     const dim3 per_cand((unsigned)((n + 3) / 4)), wg(256);
     const auto init = [&] {
-        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
-            hipLaunchKernelGGL((sp_prune_init_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        by_dim_lazy_obj(D, lazy, obj, [&](auto d, auto lz, auto o) {
+            hipLaunchKernelGGL((sp_prune_init_kernel<decltype(d)::value, decltype(lz)::value, decltype(o)::value>), per_cand, wg, 0, s, a, z);
         });
     };
-    const auto stage1 = [&] { hipLaunchKernelGGL(sp_prune_argmin_kernel, dim3((unsigned)np), wg, 0, s, a); };
+    const auto stage1 = [&] {
+        if (snoop) hipLaunchKernelGGL(sp_prune_argmin_kernel<OBJ_STAT>, dim3((unsigned)np), wg, 0, s, a);
+        else hipLaunchKernelGGL(sp_prune_argmin_kernel<OBJ_LOSS>, dim3((unsigned)np), wg, 0, s, a);
+    };
     const auto stage2 = [&] {
-        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
-            hipLaunchKernelGGL((sp_prune_pick_kernel<decltype(d)::value, decltype(lz)::value>), dim3(1), wg, 0, s, a, z);
+        by_dim_lazy_obj(D, lazy, obj, [&](auto d, auto lz, auto o) {
+            hipLaunchKernelGGL((sp_prune_pick_kernel<decltype(d)::value, decltype(lz)::value, decltype(o)::value>), dim3(1), wg, 0, s, a, z);
         });
     };
     const auto round = [&] {
-        by_dim_lazy(D, lazy, [&](auto d, auto lz) {
-            hipLaunchKernelGGL((sp_prune_round_kernel<decltype(d)::value, decltype(lz)::value>), per_cand, wg, 0, s, a, z);
+        by_dim_lazy_obj(D, lazy, obj, [&](auto d, auto lz, auto o) {
+            hipLaunchKernelGGL((sp_prune_round_kernel<decltype(d)::value, decltype(lz)::value, decltype(o)::value>), per_cand, wg, 0, s, a, z);
         });
     };
     const auto gather = [&] { hipLaunchKernelGGL(sp_prune_gather_kernel, dim3((unsigned)((n + 255) / 256)), wg, 0, s, a); };
@@ -2974,10 +3082,14 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
         a.joint = joint; a.ld = ld;
         a.J = (double *)dJ.p; a.L = (double *)dL.p; a.C = (double *)dC.p; a.hist = (double *)dhist.p;
         a.loss = (double *)dloss.p; a.margin = (double *)dmargin.p; a.tr0 = (double *)dtr0.p; a.state = (int32_t *)dstate.p;
-        a.pg = (double *)dpg.p; a.pi = (int32_t *)dpi.p; a.ctl = (int32_t *)dctl.p; a.pubC = (double *)dpub.p; a.kldsum = (double *)dksum.p;
+        a.pg = (double *)dpg.p; a.pi = (int32_t *)dpi.p; a.ctl = (int32_t *)dctl.p; a.pubC = (double *)dpub.p;
+        if (snoop) a.e = (double *)de.p;
+        else a.kldsum = (double *)dksum.p;
         a.sel = (int32_t *)dsel.p; a.cl = (double *)dcl.p; a.ck = (double *)dck.p;
         a.final_loss = (double *)dfl.p; a.final_margin = (double *)dfm.p; a.status = (int32_t *)dstatus.p;
-        a.n = n; a.kk = kk; a.np = np; a.max_loss = max_loss; a.max_kld = max_kld; a.min_margin = min_margin;
+        a.n = n; a.kk = kk; a.np = np; a.max_kld = max_kld; a.min_margin = min_margin;
+        if (snoop) a.min_stat = limit;
+        else a.max_loss = limit;
         if (lazy) {   // round 0 from the pair blocks; the rounds follow in `post`, on the factor
             a.joint = nullptr; a.ld = 0;
             z.blocks = joint; z.pslot = (const int32_t *)dpslot.p; z.rank = (int32_t *)dctl.p + 4; z.L = look; z.ca = z.cb = -1;
@@ -3001,14 +3113,36 @@ int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, co
     HIPCHK(hipMemcpy(ctl, dctl.p, sizeof ctl, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(pruned, dsel.p, (size_t)kk * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cond_loss, dcl.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(kld, dck.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
+    if (kld) HIPCHK(hipMemcpy(kld, dck.p, (size_t)kk * 8, hipMemcpyDeviceToHost));
+    if (redundancy) {   // D - tr(L_i^T C_ii(0) L_i); NaN where Omega is not PD
+        HIPCHK(hipMemcpy(redundancy, dtr0.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) redundancy[i] = (double)D - redundancy[i];
+    }
     if (final_loss) HIPCHK(hipMemcpy(final_loss, dfl.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (final_margin) HIPCHK(hipMemcpy(final_margin, dfm.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, dstatus.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     *npruned = ctl[0];
     stats.rounds = ctl[0];
-    stats.prune_seconds = 1e-3 * ms;
+    stats.seconds = 1e-3 * ms;
     return 0;
+}
+
+int hip_sparse_prune(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                     int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double max_loss, double max_kld,
+                     double min_margin, int32_t *pruned, double *cond_loss, double *kld, double *final_loss, double *final_margin, int32_t *status,
+                     int *npruned, spg_prune_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
+    return greedy_edges(OBJ_LOSS, "edge pruning", stream, in, va, vb, dst, ld, nblk, joint_len, eidx, sa, sb, n, kk, max_loss, max_kld, min_margin, pruned,
+                        cond_loss, kld, final_loss, final_margin, nullptr, status, npruned, {stats.solve, stats.rounds, stats.prune_seconds}, err, errlen, lazy);
+}
+
+// spg_graph_detect_outliers: flagged / stat: kk entries; final_stat, final_margin, redundancy, status: n each, may be nullptr
+int hip_sparse_detect(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                      int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double min_stat, double min_margin,
+                      int32_t *flagged, double *stat, double *final_stat, double *final_margin, double *redundancy, int32_t *status, int *nflagged,
+                      spg_outlier_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy) {
+    return greedy_edges(OBJ_STAT, "outlier detection", stream, in, va, vb, dst, ld, nblk, joint_len, eidx, sa, sb, n, kk, min_stat, 0.0, min_margin, flagged,
+                        stat, nullptr, final_stat, final_margin, redundancy, status, nflagged, {stats.solve, stats.rounds, stats.detect_seconds}, err, errlen,
+                        lazy);
 }
 
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi
+from . import abi, chi2
 from .lib import Context, check, load
 
 _f64p, _i32p, _i64p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -502,6 +502,40 @@ class GraphWrapperHIP:
         idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
         out = self.pruneCandidates(idx, k, max_loss, max_kld, min_margin, fixed_id)
         self.removeEdges(idx[out["pruned"]])
+        return out
+
+    def detectOutliers(self, edge_idx, k, min_stat=0.0, significance=None, min_margin=0.0, fixed_id=-1):
+        """Greedy data snooping over the listed live binary edges (indices into the order of edges(); include/spg.h:
+        spg_graph_detect_outliers): each round flags the edge with the largest leave-one-out chi^2 statistic given the ones
+        already flagged (ties: the lowest index) and re-conditions the others, on the device, without modifying the graph.
+        The stored estimates are taken as the minimiser: call optimize() first. Stops when the best statistic is < min_stat
+        (<= 0: no threshold); significance=p sets min_stat to the chi^2_D quantile at 1 - p. An edge whose removal would
+        make the information singular to min_margin (<= 0: 1e-6) cannot be tested. Returns a dict: flagged int32[r]
+        (indices into edge_idx, in order), stat float64[r], final_stat, final_margin, redundancy float64[n], status
+        int32[n] (abi.OUTLIER_*). Stats (abi.OutlierStats) in `last_covariance_stats`."""
+        if significance is not None:
+            min_stat = chi2.chi2_quantile(1.0 - float(significance), self.d)
+        st = abi.OutlierStats()
+        idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
+        n = len(idx)
+        cap = max(min(int(k), n), 0)
+        sel, cs = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), np.nan)
+        out = {"final_stat": np.full(n, np.nan), "final_margin": np.full(n, np.nan), "redundancy": np.full(n, np.nan),
+               "status": np.zeros(n, np.int32)}
+        rc = self.L.spg_graph_detect_outliers(self.h, int(fixed_id), _p(idx, C.c_int32), n, int(k), float(min_stat), float(min_margin),
+                                              _p(sel, C.c_int32), _p(cs, C.c_double), cap, _p(out["final_stat"], C.c_double),
+                                              _p(out["final_margin"], C.c_double), _p(out["redundancy"], C.c_double),
+                                              _p(out["status"], C.c_int32), C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "detectOutliers")
+        self.last_covariance_stats = st.asdict()
+        out["flagged"], out["stat"], out["min_stat"] = sel[:rc].copy(), cs[:rc].copy(), float(min_stat)
+        return out
+
+    def rejectOutliers(self, edge_idx, k, min_stat=0.0, significance=None, min_margin=0.0, fixed_id=-1):
+        """detectOutliers followed by removeEdges of what it flagged; returns detectOutliers' dict."""
+        idx = np.ascontiguousarray(edge_idx, np.int32).reshape(-1)
+        out = self.detectOutliers(idx, k, min_stat, significance, min_margin, fixed_id)
+        self.removeEdges(idx[out["flagged"]])
         return out
 
     def marginalKullbackLeibler(self, other, fixed_id=-1):

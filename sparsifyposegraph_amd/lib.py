@@ -80,6 +80,8 @@ SYMBOLS = {
                                               _f64p, _i32p, C.POINTER(abi.SelectStats)]),
     "spg_graph_prune_candidates": (C.c_int, [C.c_void_p, C.c_int32, _i32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _i32p, _f64p, _f64p,
                                              C.c_int, _f64p, _f64p, _i32p, C.POINTER(abi.PruneStats)]),
+    "spg_graph_detect_outliers": (C.c_int, [C.c_void_p, C.c_int32, _i32p, C.c_int, C.c_int, C.c_double, C.c_double, _i32p, _f64p, C.c_int, _f64p, _f64p,
+                                            _f64p, _i32p, C.POINTER(abi.OutlierStats)]),
     "spg_graph_remove_edges": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),

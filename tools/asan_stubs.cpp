@@ -31,5 +31,6 @@ int hip_sparse_cov_solve(void *, const DenseGraphIn &, const int32_t *, const in
 int hip_sparse_relative(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, int, const double *, double *, double *, double *, double *, double *, int32_t *, spg_cov_solve_stats &, char *, size_t) { return SPG_ENODEV; }
 int hip_sparse_select(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *, int, double, double, int32_t *, double *, double *, int32_t *, int *, spg_select_stats &, char *, size_t, const GreedyLazyIn *) { return SPG_ENODEV; }
 int hip_sparse_prune(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, int, int, double, double, double, int32_t *, double *, double *, double *, double *, int32_t *, int *, spg_prune_stats &, char *, size_t, const GreedyLazyIn *) { return SPG_ENODEV; }
+int hip_sparse_detect(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, int, int, double, double, int32_t *, double *, double *, double *, double *, int32_t *, int *, spg_outlier_stats &, char *, size_t, const GreedyLazyIn *) { return SPG_ENODEV; }
 int hip_sparse_marginal_kld(void *, const DenseGraphIn &, const DenseGraphIn &, const int32_t *, const int32_t *, int, const int64_t *, const int64_t *, double *, spg_cov_stats &, char *, size_t) { return SPG_ENODEV; }
 }

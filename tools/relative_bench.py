@@ -5,6 +5,7 @@ the current relative pose, Omega = the generator's info_diag), relativeCovarianc
     python tools/relative_bench.py [--mode score|relative|pairs] [--poses 100000] [--ring 400] [--vertex 50000] [--runs 5]
     python tools/relative_bench.py --mode select --k K --candidates N [--endpoints 7000]
     python tools/relative_bench.py --mode prune --k K --candidates N --endpoints M
+    python tools/relative_bench.py --mode outliers --k K --candidates N --endpoints M
 
 --mode select: selectCandidates of N random pairs without a common edge, drawn over a random pool of at most --endpoints
 (at most 7 000) vertices, Omega of an existing edge, z = the current relative pose plus noise; select_seconds, rounds and
@@ -15,6 +16,10 @@ endpoints are those of spg_select_stats. The same process also times one scoreCa
 (every edge inside the block, at most N of them); prune_seconds, rounds and endpoints are those of spg_prune_stats. The
 same process times selectCandidates at the same k on a list with the same endpoint pairs (z = the current relative pose
 plus noise, Omega of an existing edge), so the column-solve part is the same and select_seconds stands beside prune_seconds.
+
+--mode outliers: detectOutliers (no threshold: k rounds) of the candidate list of --mode prune at the generator's poses;
+detect_seconds, rounds and endpoints are those of spg_outlier_stats. The rounds are the pruning's plus a D-vector per
+candidate, so detect_seconds stands beside the prune_seconds of a --mode prune --skip-select run with the same arguments.
 
 device_seconds and solve_seconds are those of spg_cov_solve_stats (HIP events: factorisation, column solves, selected
 inverse, assembly and, for score / relative, sp_relative_kernel); wall_seconds is the host clock around the whole call
@@ -40,7 +45,7 @@ from sparsifyposegraph_amd.graph import GraphWrapperHIP  # noqa: E402
 from sparsifyposegraph_amd.lib import Context  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=("score", "relative", "pairs", "select", "prune"), default="score")
+ap.add_argument("--mode", choices=("score", "relative", "pairs", "select", "prune", "outliers"), default="score")
 ap.add_argument("--k", type=int, default=10)
 ap.add_argument("--candidates", type=int, default=2000)
 ap.add_argument("--endpoints", type=int, default=7000)
@@ -76,7 +81,7 @@ if args.mode == "select":
         if (min(a, b), max(a, b)) not in adj:
             far.append((a, b))
     star = np.array(far, np.int32)
-if args.mode == "prune":
+if args.mode in ("prune", "outliers"):
     lo = max(0, min(args.vertex, len(ids) - args.endpoints))
     pool = {int(v) for v in ids[lo:lo + args.endpoints]}
     e = hg.edges()
@@ -84,7 +89,7 @@ if args.mode == "prune":
     eidx = np.array(inside[:args.candidates], np.int32)
     star = np.array([e["vert_ids"][e["vert_off"][k]:e["vert_off"][k + 1]] for k in eidx], np.int32)
     rng = np.random.default_rng(2024)
-    if not args.skip_select:
+    if args.mode == "prune" and not args.skip_select:
         meas = hg.relativeCovariances(star)[0]
         meas[:, :3] += 0.01 * rng.normal(size=(len(star), 3))
         info = np.tile(g["edge_data"][0, 7:], (len(star), 1))
@@ -99,9 +104,21 @@ if args.mode == "prune":
             st = hg.last_covariance_stats
             out["device"].append(st["device_seconds"]); out["solve"].append(st["solve_seconds"]); out[key].append(st[key])
         return r, st, out
+    med = statistics.median
+    if args.mode == "outliers":
+        ro, so, to = timed(lambda: hg.detectOutliers(eidx, args.k), "detect_seconds")
+        print(json.dumps({
+            "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {len(eidx)} existing edges inside a block of {len(pool)} vertices",
+            "mode": "outliers", "k": args.k, "candidates": len(eidx), "runs": args.runs, "rounds": so["rounds"], "endpoints": so["endpoints"],
+            "detect_seconds": med(to["detect_seconds"]), "detect_seconds_min": min(to["detect_seconds"]),
+            "detect_seconds_max": max(to["detect_seconds"]),
+            "device_seconds": med(to["device"]), "device_seconds_min": min(to["device"]), "device_seconds_max": max(to["device"]),
+            "solve_seconds": med(to["solve"]), "wall_seconds": med(to["wall"]), "columns": so["columns"], "rhs_batches": so["rhs_batches"],
+            "stat_first": float(ro["stat"][0]) if len(ro["stat"]) else 0.0, "stat_last": float(ro["stat"][-1]) if len(ro["stat"]) else 0.0,
+            "untestable": int((ro["status"] == 2).sum()), **greedy_extra()}), flush=True)
+        sys.exit(0)
     rp, sp, tp = timed(lambda: hg.pruneCandidates(eidx, args.k), "prune_seconds")
     gx = greedy_extra()
-    med = statistics.median
     if args.skip_select:
         print(json.dumps({
             "workload": f"synthetic SE3, {args.poses} poses, ring {args.ring}: {len(eidx)} existing edges inside a block of {len(pool)} vertices",
