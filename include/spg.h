@@ -620,6 +620,70 @@ typedef struct {
 /* of the context's last spg_graph_select_candidates / _prune_candidates / _detect_outliers call that reached the device (all zero before) */
 int spg_ctx_greedy_stats(spg_ctx *ctx, spg_greedy_stats *out);
 
+/* ---- joint compatibility of candidates ---------------------------------------------------------------------
+ * Which of n candidate edges agree with each other. The gate of the calls above tests each candidate alone against the
+ * graph; where drift makes P = J Sigma J^T large against Omega^-1 that test is weak, and a group of aliased closures with a
+ * common wrong offset passes it. Here, with J_i = [Ja Jb], e_i and Omega_i = L_i L_i^T of spg_graph_score_candidates at the
+ * stored estimates and Sigma in the gauge of fixed_id (zero blocks stand for the fixed vertex; Omega^-1 is never formed):
+ *   U_i  = L_i^T J_i (D x 2D),   w_i = L_i^T e_i,   M_ij = delta_ij I + U_i Sigma_(ai bi),(aj bj) U_j^T (D x D)
+ *   d2(S) = w_S^T (M_SS)^-1 w_S = e_S^T (blockdiag Omega^-1 + A_S Sigma A_S^T)^-1 e_S      chi^2 with |S| D degrees of
+ *                                                       freedom when every member of S is an inlier; M_SS >= I always
+ * Eligible: as the selection. Omega finite and positive definite (else SPG_CAND_INFO_NOT_PD) and, when max_d2 > 0,
+ * d2_i = d2({i}) <= max_d2 (else SPG_CAND_GATED); d2_i is the d2 of spg_graph_score_candidates.
+ * Stage 1, the pair test. For every unordered eligible pair i < j, d2_ij = d2({i, j}) by block elimination with i first,
+ * D x D work only: d2_ij = d2_i + |G^-1 (w_j - M_ji M_ii^-1 w_i)|^2 with G G^T = M_jj - M_ji M_ii^-1 M_ij. The pair is
+ * consistent iff d2_ij <= pair_max_d2; a d2_ij that is not finite is inconsistent. Each unordered pair is computed once and
+ * both adjacency bits come from that one comparison: the consistency graph is exactly symmetric. It lives on the device as
+ * n rows of ceil(n / 64) 64-bit words (bit j of row i), the diagonal clear, the rows of ineligible candidates empty.
+ * Stage 2, the largest consistent set, a deterministic integer heuristic. For every eligible seed s: R = (s), P = N(s);
+ * while P is not empty take v = argmax over u in P of |N(u) & P| (ties: the lowest index), append v to R and set
+ * P = P & N(v). The answer is the longest R (ties: the lowest seed), its members in the order they were added. Every R is
+ * a clique of the consistency graph that no vertex extends; it is not guaranteed to be a maximum clique.
+ * Stage 3, the sequential joint gate. The members of that set are walked in ascending d2_i (ties: the lowest index),
+ * S = {} and D2 = 0 at the start. For member i the left-looking block-Cholesky step
+ *   G_iS = M_iS G_SS^-T,   G_ii G_ii^T = M_ii - G_iS G_iS^T,   y_i = G_ii^-1 (w_i - G_iS y_S),   t = D2 + |y_i|^2 = d2(S + {i})
+ * is formed, and i is accepted iff joint_max_d2 == NULL or t <= joint_max_d2[|S|] (a t that is not finite is a rejection).
+ * Accepted: the block row is appended, D2 = t, SPG_CAND_SELECTED. Rejected: the row is dropped, SPG_CAND_INCOMPATIBLE. The
+ * walk stops after k acceptances; members never examined, and eligible candidates outside the set, stay SPG_CAND_SCORED.
+ * The call always takes the joint block of the m distinct non-fixed endpoints (m D <= 46 000, as SPG_GREEDY_JOINT;
+ * spg_ctx_set_greedy_method is ignored here). SPG_ECAPACITY, before anything is allocated: n above 16 384, m D above
+ * 46 000, or the joint block, the consistency graph, the stage-3 workspace ((min(k, n) D)^2 doubles of factor plus the
+ * rows) and a requested pair_d2 together beyond free HBM (1 GB kept free). Argument errors as spg_graph_select_candidates
+ * (the text names the pair), and pair_max_d2 <= 0, a clique_cap below n with clique given, a pair_cap below n^2 with pair_d2
+ * given: SPG_EINVAL before the backend is touched; SPG_ESTATE without HIP. The graph is not modified and its robust kernel
+ * is ignored. */
+enum { SPG_CAND_INCOMPATIBLE = 4 };
+typedef struct {
+    spg_cov_solve_stats solve;   /* the covariance part; its device_seconds covers the three stages too */
+    int32_t endpoints;           /* m */
+    int32_t eligible;            /* candidates that took part in the pair test */
+    int64_t consistent_pairs;    /* edges of the consistency graph */
+    int32_t clique_size, seed;   /* stage 2: the size of the set and the seed that reached it (-1: nobody eligible) */
+    double pair_seconds;         /* HIP-event times: the per-candidate terms and stage 1, */
+    double clique_seconds;       /* stage 2, */
+    double verify_seconds;       /* stage 3 */
+} spg_compat_stats;
+/* ij, records, n, max_d2: as spg_graph_select_candidates. joint_max_d2: min(k, n) thresholds (entry p gates the set of p + 1)
+ * or NULL. compatible, joint_d2: min(k, n) entries, the accepted candidates in order and d2(S) after each; entries beyond
+ * the return value are -1 / NaN. clique (clique_cap >= n entries, may be NULL): the stage-2 set in order of construction,
+ * -1 beyond stats->clique_size. d2, degree, status: n each, each may be NULL; degree = the candidate's row sum of the
+ * consistency graph. pair_d2 (pair_cap >= n^2, may be NULL): n x n, exactly symmetric, the diagonal = d2_i, NaN in the rows
+ * and columns of ineligible candidates. Returns the number accepted; with cap < min(k, n) (or compatible / joint_d2 NULL)
+ * returns min(k, n) and writes nothing. n = 0 or k = 0 returns 0. */
+int spg_graph_compatible_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k,
+                                    double max_d2, double pair_max_d2, const double *joint_max_d2,
+                                    int32_t *compatible, double *joint_d2, int cap,
+                                    int32_t *clique, int clique_cap,
+                                    double *d2, int32_t *degree, int32_t *status,
+                                    double *pair_d2, int64_t pair_cap,
+                                    spg_compat_stats *stats);
+/* Stage 2 alone on a caller's consistency graph, for a metric of the caller's own (inter-robot closures with no common
+ * graph). adj: n rows of ceil(n / 64) words, bit j of row i. SPG_EINVAL if adj is not symmetric, has a diagonal bit set or
+ * has bits at or beyond n; SPG_ECAPACITY for n above 16 384; SPG_ESTATE without HIP. Returns the size of the set; n = 0
+ * returns 0. clique (may be NULL): the members in order of construction, written when cap >= the size. seed (may be NULL):
+ * the seed that reached it. */
+int spg_ctx_max_clique(spg_ctx *ctx, int n, const uint64_t *adj, int32_t *clique, int cap, int32_t *seed);
+
 /* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is
  * canonicalised first, as spg_graph_get_edges does). Survivors keep their relative order. Bridges may be removed: a
  * disconnected graph later shows as SPG_ENOTPD. An index out of range or listed twice and an active stepwise

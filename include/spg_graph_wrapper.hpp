@@ -595,6 +595,48 @@ public:
         if (status) status->assign(st.begin(), st.begin() + n);
         return out;
     }
+    // Which candidates agree with each other (include/spg.h: spg_graph_compatible_candidates): the pairwise joint test at
+    // pair_max_d2, the largest consistent set, then the sequential joint gate (member p + 1 against joint_max_d2[p]; an empty
+    // vector: no joint gate) until k are accepted. max_d2 > 0 gates each candidate alone first. The graph is not modified.
+    struct CompatResult {
+        std::vector<int> compatible;      // indices into cands, in order of acceptance
+        std::vector<double> joint_d2;     // the joint distance after each acceptance
+        std::vector<int> clique;          // the consistent set, in order of construction
+        std::vector<double> d2;           // per candidate
+        std::vector<int> degree, status;  // per candidate: neighbours in the consistency graph, SPG_CAND_*
+    };
+    CompatResult compatibleCandidates(const std::vector<Candidate> &cands, int k, double max_d2, double pair_max_d2,
+                                      const std::vector<double> &joint_max_d2 = {}, int fixed_id = -1, spg_compat_stats *stats = nullptr) {
+        const int d = spg_graph_pose_dim(_g), n = (int)cands.size();
+        std::vector<int32_t> ij;
+        std::vector<double> rec;
+        for (const Candidate &c : cands) {
+            if (c.information.rows() != d || c.information.cols() != d) throw std::runtime_error("compatibleCandidates: information must be d x d");
+            const VectorXd &z = c.measurement;
+            if ((int)z.size() != (d == 3 ? 3 : 7)) throw std::runtime_error("compatibleCandidates: the measurement does not match the graph's pose dimension");
+            ij.push_back(c.from); ij.push_back(c.to);
+            rec.insert(rec.end(), z.begin(), z.end());
+            for (int i = 0; i < d; i++) for (int j = i; j < d; j++) rec.push_back(c.information(i, j));
+        }
+        const int cap = std::max(std::min(k, n), 0);
+        if (!joint_max_d2.empty() && (int)joint_max_d2.size() < cap) throw std::runtime_error("compatibleCandidates: joint_max_d2 must have min(k, n) entries");
+        std::vector<int32_t> sel((size_t)std::max(cap, 1)), clq((size_t)std::max(n, 1)), deg(clq.size()), st(clq.size());
+        std::vector<double> jd(sel.size()), d2(clq.size());
+        spg_compat_stats cs{};
+        const int r = spg_graph_compatible_candidates(_g, fixed_id, ij.data(), rec.data(), n, k, max_d2, pair_max_d2,
+                                                      joint_max_d2.empty() ? nullptr : joint_max_d2.data(), sel.data(), jd.data(), cap, clq.data(), n,
+                                                      d2.data(), deg.data(), st.data(), nullptr, 0, &cs);
+        check(std::min(r, 0), "compatibleCandidates");
+        CompatResult out;
+        out.compatible.assign(sel.begin(), sel.begin() + r);
+        out.joint_d2.assign(jd.begin(), jd.begin() + r);
+        out.clique.assign(clq.begin(), clq.begin() + std::max(cs.clique_size, 0));
+        out.d2.assign(d2.begin(), d2.begin() + n);
+        out.degree.assign(deg.begin(), deg.begin() + n);
+        out.status.assign(st.begin(), st.begin() + n);
+        if (stats) *stats = cs;
+        return out;
+    }
     // Greedy choice of up to k of the listed live binary edges (indices into the order of spg_graph_get_edges) by
     // conditional information loss (include/spg.h: spg_graph_prune_candidates); the graph is not modified.
     struct PruneResult {

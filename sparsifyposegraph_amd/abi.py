@@ -118,6 +118,22 @@ class SelectStats(C.Structure):
         return d
 
 
+# a further value of spg_graph_compatible_candidates
+CAND_INCOMPATIBLE = 4
+
+
+class CompatStats(C.Structure):
+    """spg_compat_stats (include/spg.h)"""
+    _fields_ = [("solve", CovSolveStats), ("endpoints", C.c_int32), ("eligible", C.c_int32), ("consistent_pairs", C.c_int64),
+                ("clique_size", C.c_int32), ("seed", C.c_int32), ("pair_seconds", C.c_double), ("clique_seconds", C.c_double),
+                ("verify_seconds", C.c_double)]
+
+    def asdict(self):
+        d = self.solve.asdict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_[1:]})
+        return d
+
+
 # SPG_PRUNE_* (include/spg.h): status of a candidate of spg_graph_prune_candidates
 PRUNE_KEPT, PRUNE_INFO_NOT_PD, PRUNE_BRIDGE, PRUNE_PRUNED = 0, 1, 2, 3
 

@@ -641,6 +641,112 @@ extern "C" int spg_graph_select_candidates(spg_graph *g, int32_t fixed_id, const
     return select_call(g, fixed_id, ij, records, n, k, min_gain, max_d2, selected, cond_gain, cap, final_gain, status, stats);
 }
 
+// ================================================================================= joint compatibility of candidates
+namespace {
+constexpr int kCompatMaxN = 16384;
+// set_err with numbers in the text
+template <class... A>
+int fail(spg_ctx *c, int code, const char *fmt, A... a) {
+    snprintf(c->err, sizeof c->err, fmt, a...);
+    return code;
+}
+// spg_graph_compatible_candidates: the checks, the endpoint set and the slots of select_call, the joint block always.
+int compat_call(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k, double max_d2, double pair_max_d2,
+                const double *joint_max_d2, int32_t *compatible, double *joint_d2, int cap, int32_t *clique, int clique_cap, double *d2, int32_t *degree,
+                int32_t *status, double *pair_d2, int64_t pair_cap, spg_compat_stats *stats) {
+    const char *what = "spg_graph_compatible_candidates";
+    if (!g || n < 0 || (n > 0 && (!ij || !records))) return SPG_EINVAL;
+    if (k < 0) return set_err(g->ctx, SPG_EINVAL, "%s: k is negative", what);
+    if (!(pair_max_d2 > 0.0)) return set_err(g->ctx, SPG_EINVAL, "%s: pair_max_d2 must be positive", what);
+    if (clique && clique_cap < n) return set_err(g->ctx, SPG_EINVAL, "%s: clique_cap is below n", what);
+    if (pair_d2 && pair_cap < (int64_t)n * n) return set_err(g->ctx, SPG_EINVAL, "%s: pair_cap is below n^2", what);
+    if (g->active) return set_err(g->ctx, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return set_err(g->ctx, SPG_EINVAL, "%s: the fixed vertex is not in the graph", what);
+    const int D = g->d;
+    std::vector<int32_t> S, ca((size_t)n), cb((size_t)n), sa((size_t)n), sb((size_t)n);
+    std::unordered_map<int32_t, int32_t> slot_of;
+    for (int i = 0; i < n; i++) {
+        int ia, ib;
+        if (int rc = check_pair(g, what, i, ij, records, ia, ib)) return rc;
+        ca[i] = ia; cb[i] = ib;
+        const int32_t v[2] = {ia, ib};
+        int32_t sl[2];
+        for (int e = 0; e < 2; e++) {
+            if (v[e] == fixed) { sl[e] = -1; continue; }
+            auto it = slot_of.emplace(v[e], (int32_t)S.size());
+            if (it.second) S.push_back(v[e]);
+            sl[e] = it.first->second;
+        }
+        sa[i] = sl[0]; sb[i] = sl[1];
+    }
+    const int kk = std::min(k, n);
+    if (kk == 0) return 0;
+    const int64_t m = (int64_t)S.size(), W = m * D, need = W * W;
+    if (n > kCompatMaxN) return fail(g->ctx, SPG_ECAPACITY, "%s: %d candidates, limited to %d", what, n, kCompatMaxN);
+    if (W > 46000) {
+        snprintf(g->ctx->err, sizeof g->ctx->err, "%s: %lld distinct endpoints, limited to 46k variables, the bound of spg_graph_joint_marginal_covariance",
+                 what, (long long)m);
+        return SPG_ECAPACITY;
+    }
+    if (!compatible || !joint_d2 || cap < kk) return kk;
+    std::vector<int32_t> va, vb;
+    std::vector<int64_t> dst;
+    va.reserve((size_t)(m * m)); vb.reserve((size_t)(m * m)); dst.reserve((size_t)(m * m));
+    for (int64_t a = 0; a < m; a++)
+        for (int64_t b = 0; b < m; b++) { va.push_back(S[a]); vb.push_back(S[b]); dst.push_back(a * D * W + b * D); }
+    DenseStage st;
+    const int staged = cov_stage(g, fixed, order, {&va, &vb}, need, nullptr, what, st);
+    if (staged < 0) return staged;
+    spg_compat_stats cs{};
+    cs.endpoints = (int32_t)m;
+    int nacc = 0;
+    const spg::CompatOut out{compatible, joint_d2, clique, d2, degree, status, pair_d2};
+    if (int rc = spg::hip_sparse_compat(spg::hip_backend_stream(&g->ctx->be), st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), need,
+                                        ca.data(), cb.data(), sa.data(), sb.data(), n, records, kk, max_d2, pair_max_d2, joint_max_d2, out, &nacc, cs,
+                                        g->ctx->err, sizeof g->ctx->err)) return rc;
+    if (stats) *stats = cs;
+    return nacc;
+}
+}  // namespace
+
+extern "C" int spg_graph_compatible_candidates(spg_graph *g, int32_t fixed_id, const int32_t *ij, const double *records, int n, int k, double max_d2,
+                                               double pair_max_d2, const double *joint_max_d2, int32_t *compatible, double *joint_d2, int cap,
+                                               int32_t *clique, int clique_cap, double *d2, int32_t *degree, int32_t *status, double *pair_d2,
+                                               int64_t pair_cap, spg_compat_stats *stats) {
+    return compat_call(g, fixed_id, ij, records, n, k, max_d2, pair_max_d2, joint_max_d2, compatible, joint_d2, cap, clique, clique_cap, d2, degree, status,
+                       pair_d2, pair_cap, stats);
+}
+
+extern "C" int spg_ctx_max_clique(spg_ctx *ctx, int n, const uint64_t *adj, int32_t *clique, int cap, int32_t *seed) {
+    const char *what = "spg_ctx_max_clique";
+    if (!ctx || n < 0) return SPG_EINVAL;
+    if (n == 0) return 0;
+    if (!adj) return SPG_EINVAL;
+    if (n > kCompatMaxN) return fail(ctx, SPG_ECAPACITY, "%s: %d vertices, limited to %d", what, n, kCompatMaxN);
+    const int nw = (n + 63) / 64;
+    for (int i = 0; i < n; i++)
+        for (int w = 0; w < nw; w++) {
+            uint64_t bits = adj[(size_t)i * nw + w];
+            if (w == nw - 1 && (n & 63) && (bits >> (n & 63))) return fail(ctx, SPG_EINVAL, "%s: row %d has bits at or beyond n", what, i);
+            while (bits) {
+                const int j = w * 64 + __builtin_ctzll(bits);
+                bits &= bits - 1;
+                if (j == i) return fail(ctx, SPG_EINVAL, "%s: the diagonal bit of row %d is set", what, i);
+                if (!((adj[(size_t)j * nw + (i >> 6)] >> (i & 63)) & 1)) return fail(ctx, SPG_EINVAL, "%s: not symmetric at (%d, %d)", what, i, j);
+            }
+        }
+    if (!ctx->is_hip) return set_err(ctx, SPG_ESTATE, "%s needs the HIP backend", what);
+    std::vector<int32_t> members((size_t)n);
+    int size = 0;
+    int32_t sd = -1;
+    if (int rc = spg::hip_max_clique(spg::hip_backend_stream(&ctx->be), n, adj, members.data(), &size, &sd, ctx->err, sizeof ctx->err)) return rc;
+    if (clique && cap >= size) std::copy(members.begin(), members.begin() + size, clique);
+    if (seed) *seed = sd;
+    return size;
+}
+
 // ================================================================================= greedy edge pruning, outlier detection
 namespace {
 // What spg_graph_prune_candidates and spg_graph_detect_outliers share. Candidate i is live edge edge_idx[i] in the order

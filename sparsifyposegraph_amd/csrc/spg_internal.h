@@ -158,6 +158,25 @@ int hip_sparse_detect(void *stream, const DenseGraphIn &in, const int32_t *va, c
                       int64_t joint_len, const int32_t *eidx, const int32_t *sa, const int32_t *sb, int n, int kk, double min_stat, double min_margin,
                       int32_t *flagged, double *stat, double *final_stat, double *final_margin, double *redundancy, int32_t *status, int *nflagged,
                       spg_outlier_stats &stats, char *err, size_t errlen, const GreedyLazyIn *lazy = nullptr);
+// Joint compatibility of candidates (spg_compat.inc: sp_compat_*_kernel, sp_clique_*_kernel). The sub-block
+// lists, ca / cb and the slots sa / sb as hip_sparse_select, the joint block alone. n, kk >= 1, n <= 16 384. joint_max_d2:
+// kk thresholds or nullptr. out.compatible, out.joint_d2: kk entries; clique, d2, degree, status: n each, pair_d2: n x n,
+// each may be nullptr. stats: everything but `endpoints`.
+struct CompatOut {
+    int32_t *compatible;
+    double *joint_d2;
+    int32_t *clique;
+    double *d2;
+    int32_t *degree, *status;
+    double *pair_d2;
+};
+int hip_sparse_compat(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                      int64_t joint_len, const int32_t *ca, const int32_t *cb, const int32_t *sa, const int32_t *sb, int n, const double *rec, int kk,
+                      double max_d2, double pair_max_d2, const double *joint_max_d2, const CompatOut &out, int *ncompat, spg_compat_stats &stats,
+                      char *err, size_t errlen);
+// Stage 2 alone on a caller's consistency graph (spg_ctx_max_clique): adj = n x ceil(n / 64) words, checked by the caller;
+// clique: n entries, the members in order of construction (-1 beyond *size); *seed = the winning seed.
+int hip_max_clique(void *stream, int n, const uint64_t *adj, int32_t *clique, int *size, int32_t *seed, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -3197,3 +3197,5 @@ int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseG
 }
 
 }  // namespace spg
+
+#include "spg_compat.inc"

@@ -468,6 +468,58 @@ class GraphWrapperHIP:
         out["selected"], out["cond_gain"] = sel[:rc].copy(), cg[:rc].copy()
         return out
 
+    def compatibleCandidates(self, ij, meas, info_upper, k=None, significance=0.99, max_d2=None, pair_max_d2=None, joint_max_d2=None, pairs=False,
+                             fixed_id=-1):
+        """Which of the n candidates of scoreCandidates' layout agree with each other (include/spg.h:
+        spg_graph_compatible_candidates), on the device, without modifying the graph: the joint Mahalanobis distance of
+        every pair of gated candidates against pair_max_d2 gives a consistency graph, a greedy search over every seed its
+        largest consistent set, and the members of that set pass a sequential joint gate in ascending d2 (member p + 1
+        against joint_max_d2[p]) until k are accepted (k=None: n). Thresholds left None come from `significance`: the
+        chi^2 quantile with D degrees of freedom for max_d2 (0 = no gate), 2D for pair_max_d2, pD, p = 1 .. min(k, n),
+        for joint_max_d2 (False = no joint gate). Returns a dict: compatible int32[r] (indices into the list, in order of
+        acceptance), joint_d2 float64[r] (the joint distance after each), clique int32[c] (the consistent set in order of
+        construction), d2 float64[n], degree int32[n], status int32[n] (abi.CAND_*), pair_d2 float64[n, n] when `pairs`,
+        and the thresholds used. Stats (abi.CompatStats) in `last_covariance_stats`."""
+        d, st = self.d, abi.CompatStats()
+        ij = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
+        n = len(ij)
+        ps, tri = (3 if d == 3 else 7), d * (d + 1) // 2
+        meas, info_upper = np.asarray(meas, np.float64), np.asarray(info_upper, np.float64)
+        if meas.size != n * ps or info_upper.size != n * tri:
+            raise ValueError("compatibleCandidates: meas must be n x (3|7) and info_upper n x D (D + 1) / 2")
+        rec = np.ascontiguousarray(np.concatenate([meas.reshape(n, ps), info_upper.reshape(n, tri)], axis=1))
+        k = n if k is None else int(k)
+        cap = max(min(k, n), 0)
+        q = float(significance)
+        if max_d2 is None:
+            max_d2 = chi2.chi2_quantile(q, d)
+        if pair_max_d2 is None:
+            pair_max_d2 = chi2.chi2_quantile(q, 2 * d)
+        if joint_max_d2 is None:
+            joint_max_d2 = chi2.chi2_quantile_table(q, d, cap)
+        jm = None
+        if joint_max_d2 is not False:
+            jm = np.ascontiguousarray(joint_max_d2, np.float64).reshape(-1)
+            if len(jm) < cap:
+                raise ValueError("compatibleCandidates: joint_max_d2 must have min(k, n) entries")
+        sel, jd = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), np.nan)
+        clique = np.full(max(n, 1), -1, np.int32)
+        out = {"d2": np.full(n, np.nan), "degree": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+        pd = np.full((n, n), np.nan) if pairs else None
+        rc = self.L.spg_graph_compatible_candidates(self.h, int(fixed_id), _p(ij, C.c_int32), _p(rec, C.c_double), n, k, float(max_d2),
+                                                    float(pair_max_d2), None if jm is None else _p(jm, C.c_double), _p(sel, C.c_int32),
+                                                    _p(jd, C.c_double), cap, _p(clique, C.c_int32), n, _p(out["d2"], C.c_double),
+                                                    _p(out["degree"], C.c_int32), _p(out["status"], C.c_int32),
+                                                    None if pd is None else _p(pd, C.c_double), n * n, C.byref(st))
+        check(min(int(rc), 0), self.ctx.h, "compatibleCandidates")
+        self.last_covariance_stats = st.asdict()
+        out["compatible"], out["joint_d2"] = sel[:rc].copy(), jd[:rc].copy()
+        out["clique"] = clique[:max(st.clique_size, 0)].copy()
+        out["max_d2"], out["pair_max_d2"], out["joint_max_d2"] = float(max_d2), float(pair_max_d2), None if jm is None else jm[:cap].copy()
+        if pairs:
+            out["pair_d2"] = pd
+        return out
+
     def pruneCandidates(self, edge_idx, k, max_loss=0.0, max_kld=0.0, min_margin=0.0, fixed_id=-1):
         """Greedy choice of up to k of the listed live binary edges (indices into the order of edges()) by conditional
         information loss (include/spg.h: spg_graph_prune_candidates): each round takes the edge whose removal costs the

@@ -82,6 +82,9 @@ SYMBOLS = {
                                              C.c_int, _f64p, _f64p, _i32p, C.POINTER(abi.PruneStats)]),
     "spg_graph_detect_outliers": (C.c_int, [C.c_void_p, C.c_int32, _i32p, C.c_int, C.c_int, C.c_double, C.c_double, _i32p, _f64p, C.c_int, _f64p, _f64p,
                                             _f64p, _i32p, C.POINTER(abi.OutlierStats)]),
+    "spg_graph_compatible_candidates": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int, C.c_int, C.c_double, C.c_double, _f64p, _i32p, _f64p,
+                                                  C.c_int, _i32p, C.c_int, _f64p, _i32p, _i32p, _f64p, C.c_int64, C.POINTER(abi.CompatStats)]),
+    "spg_ctx_max_clique": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), _i32p, C.c_int, _i32p]),
     "spg_graph_remove_edges": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
@@ -243,6 +246,25 @@ class Context:
         st = abi.GreedyStats()
         check(self.L.spg_ctx_greedy_stats(self.h, C.byref(st)), self.h, "spg_ctx_greedy_stats")
         return st.asdict()
+
+    def max_clique(self, adj):
+        """spg_ctx_max_clique: the greedy largest consistent set of a caller's consistency graph, on the device. adj: a
+        boolean n x n matrix, symmetric with a clear diagonal. For every seed s: R = (s), P = N(s); while P is not empty the
+        vertex of P with the most neighbours in P (ties: the lowest index) joins R and P shrinks to its neighbours. Returns a
+        dict: clique int32[size] (the longest R, ties to the lowest seed, in order of construction), seed."""
+        import numpy as np
+        a = np.asarray(adj)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("max_clique: adj must be a square matrix")
+        n = a.shape[0]
+        nw = max((n + 63) // 64, 1)
+        bits = np.zeros((n, nw * 64), np.uint8)
+        bits[:, :n] = a != 0
+        words = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8").reshape(n, nw)
+        clique, seed = np.full(max(n, 1), -1, np.int32), C.c_int32(-1)
+        rc = self.L.spg_ctx_max_clique(self.h, n, words.ctypes.data_as(C.POINTER(C.c_uint64)), clique.ctypes.data_as(_i32p), n, C.byref(seed))
+        check(rc, self.h, "spg_ctx_max_clique")
+        return {"clique": clique[:rc].copy(), "seed": int(seed.value)}
 
     def synchronize(self):
         check(self.L.spg_ctx_synchronize(self.h), self.h, "spg_ctx_synchronize")
