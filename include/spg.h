@@ -684,6 +684,58 @@ int spg_graph_compatible_candidates(spg_graph *g, int32_t fixed_id, const int32_
  * the seed that reached it. */
 int spg_ctx_max_clique(spg_ctx *ctx, int n, const uint64_t *adj, int32_t *clique, int cap, int32_t *seed);
 
+/* ---- proposal of candidates by proximity and range -----------------------------------------------------------
+ * Where the pairs ij of the calls above come from: which old poses the current poses might see. Two stages, both on the
+ * device, at the stored estimates; the graph is not modified and its robust kernel is ignored.
+ * Stage A, the geometric search. p_v = the translation of vertex v (xy / xyz). Two distinct live vertices, written with
+ * id_a < id_b, QUALIFY iff
+ *   1. dist = |p_a - p_b|_2 <= search_radius (search_radius > 0 and finite);
+ *   2. max_angle <= 0, or the rotation angle of X_a^-1 X_b is <= max_angle (SE2: |wrap(theta_b - theta_a)|, SE3:
+ *      2 atan2(|vec|, |w|) of q_a^-1 q_b);
+ *   3. min_id_gap <= 1, or id_b - id_a >= min_id_gap (the convention of spg_graph_set_robust_kernel);
+ *   4. no live edge of any kind (binary, GLC, MULTI) has both a and b among its vertices;
+ *   5. queries == NULL (every live vertex is a query), or a or b is one of the n_queries distinct live ids listed.
+ * The per-vertex cap max_per_vertex = m (0: none; above 32: SPG_EINVAL): for every query v its qualifying partners are
+ * ordered by (dist, partner id) ascending and tau_v is the m-th entry, +inf with fewer than m. A qualifying pair is KEPT
+ * iff a is a query and (dist, id_b) <= tau_a, or b is a query and (dist, id_a) <= tau_b: the symmetrised m-nearest-
+ * neighbour graph, every pair once. The kept pairs are reported in ascending (id_a, id_b) order with dist and angle (the
+ * angle also when max_angle <= 0).
+ * The search is a uniform grid with cell edge search_radius: cell coordinate floor(p / search_radius) per axis, 21 signed
+ * bits per axis in one 64-bit key, the cells in an open-addressing hash table of 2^ceil(log2(2 n_live)) slots. A pose that is
+ * not finite is SPG_EINVAL, one whose cell coordinate does not fit SPG_ECAPACITY, both with the vertex id in the text and
+ * before anything is searched. Each query tests the poses of its 3^dim cells only (stats.pairs_tested). The result does
+ * not depend on the order of the device's atomics: two calls return the same bits. The environment variable
+ * SPG_PROPOSE_TABLE_BITS=b (diagnostic) forces a table of 2^b slots: SPG_ECAPACITY when the occupied cells exceed it.
+ * Stage B, the range gate under uncertainty, runs when range > 0 (range > search_radius: SPG_EINVAL), AFTER the cap
+ * of stage A, which so bounds the covariance columns solved. For every kept pair P = J Sigma_ab J^T at z = the current
+ * relative pose, exactly what spg_graph_relative_covariances computes and at its cost (one column per distinct vertex of
+ * the greedy cover; stats.solve), stays on the device, and with rho = |t_z|, u = R_z^T t_z / rho,
+ *   sigma^2 = u^T P_tt u,   zscore = (rho - range) / sigma    (sigma = 0: -inf when rho <= range, else +inf)
+ * the pair passes iff zscore <= z_max, or rho <= range (then zscore <= 0, and the pair passes whatever sigma and z_max
+ * are). Failing pairs are dropped, the order stays. fixed_id: the gauge convention of the covariance calls; a or b may be the fixed vertex. At 100 000 poses the
+ * intended use of stage B is a query list of a few recent poses: one query against all its neighbours is one column.
+ * Errors, before the backend is touched and with the offending id in the text (SPG_EINVAL): search_radius, z_max = NaN,
+ * max_per_vertex, range, an unknown or repeated query id, an unknown fixed vertex, an active stepwise marginalisation.
+ * SPG_ESTATE without HIP. A graph with fewer than two live vertices, an empty query list or no kept pair returns 0. */
+typedef struct {
+    spg_cov_solve_stats solve;    /* stage B (all zero when range <= 0) */
+    int32_t n_cells;              /* occupied cells */
+    int32_t max_cell_population;
+    int64_t table_slots;
+    int64_t pairs_tested;         /* ordered (query, partner) distance evaluations of pass 1 */
+    int64_t n_qualifying;         /* pairs under rules 1 to 5, before the cap */
+    int64_t n_kept;               /* after the cap */
+    int64_t n_gated;              /* after stage B (= n_kept when range <= 0) */
+    double device_seconds;        /* HIP-event time of stage A alone */
+} spg_propose_stats;
+/* ij: 2 per pair; dist, angle: 1 per pair; sigma, zscore (may be NULL; written when range > 0): 1 per pair. Returns the
+ * number of pairs; writes only when ij, dist and angle are given and cap >= that number. With range <= 0 a call with
+ * cap = 0 costs the search without the fill; with range > 0 the count needs the whole of stage B. */
+int64_t spg_graph_propose_candidates(spg_graph *g, int32_t fixed_id, double search_radius, double max_angle, int32_t min_id_gap,
+                                     int32_t max_per_vertex, const int32_t *queries, int n_queries, double range, double z_max,
+                                     int32_t *ij, double *dist, double *angle, double *sigma, double *zscore, int64_t cap,
+                                     spg_propose_stats *stats);
+
 /* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is
  * canonicalised first, as spg_graph_get_edges does). Survivors keep their relative order. Bridges may be removed: a
  * disconnected graph later shows as SPG_ENOTPD. An index out of range or listed twice and an active stepwise

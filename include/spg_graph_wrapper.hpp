@@ -637,6 +637,47 @@ public:
         if (stats) *stats = cs;
         return out;
     }
+    // Loop-closure candidates by proximity and range (include/spg.h: spg_graph_propose_candidates): the pairs of live
+    // vertices within search_radius of each other (rules 1 to 5 of the header), at most the max_per_vertex nearest per query
+    // vertex, and with range > 0 those whose zscore = (rho - range) / sigma is <= z_max. An empty `queries`: every vertex
+    // is a query. The pairs come in ascending (id_a, id_b) order. The graph is not modified.
+    struct ProposeResult {
+        std::vector<std::pair<int, int>> ij;
+        std::vector<double> dist, angle;
+        std::vector<double> sigma, zscore;   // with range > 0
+        spg_propose_stats stats;
+    };
+    ProposeResult proposeCandidates(double search_radius, double max_angle = 0.0, int min_id_gap = 1, int max_per_vertex = 0,
+                                    const std::vector<int> &queries = {}, double range = 0.0, double z_max = 2.0, int fixed_id = -1) {
+        std::vector<int32_t> q(queries.begin(), queries.end());
+        const int32_t *qp = q.empty() ? nullptr : q.data();
+        ProposeResult out{};
+        // the size from stage A alone: the gate can only drop pairs of it; before it, with an empty query list, the call
+        // checks range with the other arguments and returns 0 without touching the backend
+        if (range > 0.0) {
+            const int32_t none = 0;
+            check((int)spg_graph_propose_candidates(_g, fixed_id, search_radius, max_angle, min_id_gap, max_per_vertex, &none, 0, range, z_max, nullptr,
+                                                    nullptr, nullptr, nullptr, nullptr, 0, nullptr), "proposeCandidates");
+        }
+        const int64_t cap = spg_graph_propose_candidates(_g, fixed_id, search_radius, max_angle, min_id_gap, max_per_vertex, qp, (int)q.size(),
+                                                         range > 0.0 ? 0.0 : range, z_max, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &out.stats);
+        check((int)std::min<int64_t>(cap, 0), "proposeCandidates");
+        if (cap == 0) return out;
+        const size_t room = (size_t)std::max<int64_t>(cap, 1);
+        std::vector<int32_t> ij(2 * room);
+        std::vector<double> dist(room), angle(room), sigma(room), zscore(room);
+        const int64_t n = spg_graph_propose_candidates(_g, fixed_id, search_radius, max_angle, min_id_gap, max_per_vertex, qp, (int)q.size(), range, z_max,
+                                                       ij.data(), dist.data(), angle.data(), sigma.data(), zscore.data(), cap, &out.stats);
+        check((int)std::min<int64_t>(n, 0), "proposeCandidates");
+        for (int64_t i = 0; i < n; i++) out.ij.push_back({ij[2 * i], ij[2 * i + 1]});
+        out.dist.assign(dist.begin(), dist.begin() + n);
+        out.angle.assign(angle.begin(), angle.begin() + n);
+        if (range > 0.0) {
+            out.sigma.assign(sigma.begin(), sigma.begin() + n);
+            out.zscore.assign(zscore.begin(), zscore.begin() + n);
+        }
+        return out;
+    }
     // Greedy choice of up to k of the listed live binary edges (indices into the order of spg_graph_get_edges) by
     // conditional information loss (include/spg.h: spg_graph_prune_candidates); the graph is not modified.
     struct PruneResult {

@@ -134,6 +134,19 @@ class CompatStats(C.Structure):
         return d
 
 
+class ProposeStats(C.Structure):
+    """spg_propose_stats (include/spg.h)"""
+    _fields_ = [("solve", CovSolveStats), ("n_cells", C.c_int32), ("max_cell_population", C.c_int32), ("table_slots", C.c_int64),
+                ("pairs_tested", C.c_int64), ("n_qualifying", C.c_int64), ("n_kept", C.c_int64), ("n_gated", C.c_int64),
+                ("device_seconds", C.c_double)]
+
+    def asdict(self):
+        """stage A flat (device_seconds: the search alone), stage B's covariance work under "solve" """
+        d = {k: getattr(self, k) for k, _ in self._fields_[1:]}
+        d["solve"] = self.solve.asdict()
+        return d
+
+
 # SPG_PRUNE_* (include/spg.h): status of a candidate of spg_graph_prune_candidates
 PRUNE_KEPT, PRUNE_INFO_NOT_PD, PRUNE_BRIDGE, PRUNE_PRUNED = 0, 1, 2, 3
 

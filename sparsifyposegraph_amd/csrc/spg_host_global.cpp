@@ -747,6 +747,117 @@ extern "C" int spg_ctx_max_clique(spg_ctx *ctx, int n, const uint64_t *adj, int3
     return size;
 }
 
+// ================================================================================= proposal of candidates
+// spg_graph_propose_candidates: the argument checks, the live vertices by rank (ascending id) with the CSR of the live
+// adjacency over ranks (built from the edge lists as they stand: nothing is renumbered or reordered for stage A), the
+// search on the device, and for range > 0 the kept pairs handed to the relative-covariance path with the gate behind it.
+extern "C" int64_t spg_graph_propose_candidates(spg_graph *g, int32_t fixed_id, double search_radius, double max_angle, int32_t min_id_gap,
+                                                int32_t max_per_vertex, const int32_t *queries, int n_queries, double range, double z_max, int32_t *ij,
+                                                double *dist, double *angle, double *sigma, double *zscore, int64_t cap, spg_propose_stats *stats) {
+    const char *what = "spg_graph_propose_candidates";
+    if (!g || (queries && n_queries < 0)) return SPG_EINVAL;
+    spg_ctx *c = g->ctx;
+    if (!(search_radius > 0.0) || !std::isfinite(search_radius)) return fail(c, SPG_EINVAL, "%s: search_radius %g must be positive and finite", what, search_radius);
+    if (std::isnan(max_angle)) return set_err(c, SPG_EINVAL, "%s: max_angle is not a number", what);
+    if (max_per_vertex < 0 || max_per_vertex > 32) return fail(c, SPG_EINVAL, "%s: max_per_vertex %d is outside 0 .. 32", what, (int)max_per_vertex);
+    if (std::isnan(range) || range > search_radius) return fail(c, SPG_EINVAL, "%s: range %g must not exceed search_radius %g", what, range, search_radius);
+    if (std::isnan(z_max)) return set_err(c, SPG_EINVAL, "%s: z_max is not a number", what);
+    if (g->active) return set_err(c, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int n = (int)order.size();
+    if (n == 0) return 0;
+    const int fixed = resolve_fixed(g, order, fixed_id);
+    if (fixed < 0) return fail(c, SPG_EINVAL, "%s: the fixed vertex %d is not in the graph", what, (int)fixed_id);
+    std::vector<int32_t> rank_of(g->vid.size(), -1), ids((size_t)n), qlist;
+    std::vector<int64_t> vpo((size_t)n);
+    for (int r = 0; r < n; r++) { rank_of[order[r]] = r; ids[r] = g->vid[order[r]]; vpo[r] = g->vpose[order[r]]; }
+    std::vector<uint8_t> isq((size_t)n, queries ? 0 : 1);
+    if (queries) {
+        for (int i = 0; i < n_queries; i++) {
+            const int v = live_index(g, queries[i]);
+            if (v < 0) return fail(c, SPG_EINVAL, "%s: query %d: vertex %d is not in the graph", what, i, (int)queries[i]);
+            if (isq[rank_of[v]]) return fail(c, SPG_EINVAL, "%s: query %d: vertex %d is listed twice", what, i, (int)queries[i]);
+            isq[rank_of[v]] = 1;
+        }
+    }
+    for (int r = 0; r < n; r++) if (isq[r]) qlist.push_back(r);
+    spg_propose_stats ps{};
+    if (n < 2 || qlist.empty()) { if (stats) *stats = ps; return 0; }
+    if (!c->is_hip) return set_err(c, SPG_ESTATE, "%s needs the HIP backend", what);
+    int table_bits = -1;
+    if (const char *e = getenv("SPG_PROPOSE_TABLE_BITS")) {
+        table_bits = atoi(e);
+        if (table_bits < 0 || table_bits > 30) return fail(c, SPG_EINVAL, "%s: SPG_PROPOSE_TABLE_BITS=%s is outside 0 .. 30", what, e);
+    }
+    if (int rc = sync_device(g)) return rc;
+    if (int rc = c->be.synchronize(c->be.user)) return rc;
+    c->err[0] = 0;
+    // rule 4: every two vertices of one live edge are neighbours
+    std::vector<std::pair<int32_t, int32_t>> nb;
+    for (const GEdge &ge : g->edges) {
+        if (!ge.alive) continue;
+        const int32_t *vs = edge_verts(g, ge);
+        for (int i = 0; i < ge.nv; i++)
+            for (int j = 0; j < ge.nv; j++)
+                if (i != j && rank_of[vs[i]] >= 0 && rank_of[vs[j]] >= 0) nb.push_back({rank_of[vs[i]], rank_of[vs[j]]});
+    }
+    std::sort(nb.begin(), nb.end());
+    nb.erase(std::unique(nb.begin(), nb.end()), nb.end());
+    std::vector<int32_t> adjptr((size_t)n + 1, 0), adj(nb.size());
+    for (size_t i = 0; i < nb.size(); i++) { adjptr[(size_t)nb[i].first + 1]++; adj[i] = nb[i].second; }
+    for (int r = 0; r < n; r++) adjptr[(size_t)r + 1] += adjptr[r];
+    const spg::ProposeIn in{g->d, n, (int)qlist.size(), g->dev, vpo.data(), ids.data(), isq.data(), qlist.data(), adjptr.data(), adj.data(),
+                            search_radius, max_angle, (int)min_id_gap, (int)max_per_vertex, table_bits};
+    const bool gate = range > 0.0, room = ij && dist && angle;
+    std::vector<int32_t> pij;
+    std::vector<double> pdist, pangle;
+    void *stream = spg::hip_backend_stream(&c->be);
+    // without the gate a call that cannot write asks for the count alone
+    if (int rc = spg::hip_propose_search(stream, in, gate || room, pij, pdist, pangle, ps, c->err, sizeof c->err)) return rc;
+    int64_t count = ps.n_kept;
+    ps.n_gated = count;
+    if (!gate) {
+        if (stats) *stats = ps;
+        if (!room || cap < count) return count;
+        std::copy(pij.begin(), pij.end(), ij);
+        std::copy(pdist.begin(), pdist.end(), dist);
+        std::copy(pangle.begin(), pangle.end(), angle);
+        return count;
+    }
+    std::vector<double> sg((size_t)count), zs((size_t)count);
+    if (count > 0) {
+        const int D = g->d;
+        const int64_t W = 2 * D;
+        std::vector<int32_t> va, vb, ca((size_t)count), cb((size_t)count), slot((size_t)count);
+        std::vector<int64_t> dst;
+        for (int64_t i = 0; i < count; i++) {   // the pairs are distinct: one block each, laid out as relative_call lays them
+            const int32_t v[2] = {g->index_of(pij[2 * i]), g->index_of(pij[2 * i + 1])};
+            for (int ka = 0; ka < 2; ka++)
+                for (int kb = 0; kb < 2; kb++) { va.push_back(v[ka]); vb.push_back(v[kb]); dst.push_back(i * W * W + ka * D * W + kb * D); }
+            ca[i] = v[0]; cb[i] = v[1]; slot[i] = (int32_t)i;
+        }
+        DenseStage st;
+        const int64_t blocks_len = count * W * W;
+        const int staged = cov_stage(g, fixed, order, {&va, &vb}, blocks_len, nullptr, what, st);
+        if (staged < 0) return staged;
+        if (int rc = spg::hip_propose_gate(stream, st.in, va.data(), vb.data(), dst.data(), (int32_t)W, (int64_t)va.size(), blocks_len, ca.data(), cb.data(),
+                                           slot.data(), (int)count, range, sg.data(), zs.data(), ps.solve, c->err, sizeof c->err)) return rc;
+    }
+    std::vector<int64_t> pass;
+    for (int64_t i = 0; i < count; i++) if (zs[i] <= z_max || zs[i] <= 0.0) pass.push_back(i);   // zscore <= 0: rho <= range, passes whatever z_max
+    ps.n_gated = (int64_t)pass.size();
+    if (stats) *stats = ps;
+    if (!room || cap < ps.n_gated) return ps.n_gated;
+    for (size_t k = 0; k < pass.size(); k++) {
+        const int64_t i = pass[k];
+        ij[2 * k] = pij[2 * i]; ij[2 * k + 1] = pij[2 * i + 1];
+        dist[k] = pdist[i]; angle[k] = pangle[i];
+        if (sigma) sigma[k] = sg[i];
+        if (zscore) zscore[k] = zs[i];
+    }
+    return ps.n_gated;
+}
+
 // ================================================================================= greedy edge pruning, outlier detection
 namespace {
 // What spg_graph_prune_candidates and spg_graph_detect_outliers share. Candidate i is live edge edge_idx[i] in the order

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 #include "../../include/spg.h"
 
 namespace spg {
@@ -177,6 +178,29 @@ int hip_sparse_compat(void *stream, const DenseGraphIn &in, const int32_t *va, c
 // Stage 2 alone on a caller's consistency graph (spg_ctx_max_clique): adj = n x ceil(n / 64) words, checked by the caller;
 // clique: n entries, the members in order of construction (-1 beyond *size); *seed = the winning seed.
 int hip_max_clique(void *stream, int n, const uint64_t *adj, int32_t *clique, int *size, int32_t *seed, char *err, size_t errlen);
+// Proposal of loop-closure candidates (spg_propose.inc: pp_*_kernel). Stage A: the n >= 2 live vertices by
+// rank = ascending id (vpo, id, isq: the vertex is a query; qlist: the nq ranks of the queries), adjptr / adj the CSR of the
+// live adjacency over ranks with ascending rows. table_bits < 0: 2^ceil(log2(2 n)) slots. fill = false: the count
+// (stats.n_kept) alone. ij (2 per pair, ids), dist, angle: the kept pairs in ascending (id_a, id_b) order. stats:
+// everything of stage A. A pose that is not finite or whose cell does not fit is reported with its id in err.
+struct ProposeIn {
+    int D, n, nq;
+    const void *dev_arena;
+    const int64_t *vpo;
+    const int32_t *id;
+    const uint8_t *isq;
+    const int32_t *qlist;
+    const int32_t *adjptr, *adj;
+    double radius, max_angle;
+    int min_id_gap, m, table_bits;
+};
+int hip_propose_search(void *stream, const ProposeIn &in, bool fill, std::vector<int32_t> &ij, std::vector<double> &dist, std::vector<double> &angle,
+                       spg_propose_stats &stats, char *err, size_t errlen);
+// Stage B: the sub-block lists, ca / cb and slot as hip_sparse_relative at the current relative pose; sigma, zscore: n each
+// (host), the range statistic of pp_gate_kernel. rel and cov stay on the device.
+int hip_propose_gate(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
+                     int64_t blocks_len, const int32_t *ca, const int32_t *cb, const int32_t *slot, int n, double range, double *sigma, double *zscore,
+                     spg_cov_solve_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

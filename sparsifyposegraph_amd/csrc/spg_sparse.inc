@@ -3199,3 +3199,4 @@ int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseG
 }  // namespace spg
 
 #include "spg_compat.inc"
+#include "spg_propose.inc"

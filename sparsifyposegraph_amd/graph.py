@@ -520,6 +520,47 @@ class GraphWrapperHIP:
             out["pair_d2"] = pd
         return out
 
+    def proposeCandidates(self, search_radius, max_angle=0.0, min_id_gap=1, max_per_vertex=0, queries=None, range=0.0, z_max=2.0, fixed_id=-1,
+                          stats=False):
+        """Loop-closure candidates by proximity and range (include/spg.h: spg_graph_propose_candidates), on the device,
+        without modifying the graph. Stage A: the pairs of distinct live vertices within search_radius of each other (and
+        within max_angle when > 0, at least min_id_gap ids apart when > 1, without a common live edge, with an endpoint in
+        `queries` when given), at most the max_per_vertex nearest per query vertex (0: all; symmetrised), found on a
+        uniform grid. Stage B, when range > 0: a pair stays iff zscore = (rho - range) / sigma <= z_max, sigma the
+        standard deviation of the pair's range from its relative covariance in the gauge of fixed_id; the cap of stage A
+        applies first. Returns a dict of numpy arrays in ascending (id_a, id_b) order: ij int32[n, 2], dist, angle
+        float64[n], with range > 0 also sigma and zscore; with `stats` the entry "stats" (abi.ProposeStats.asdict())."""
+        st = abi.ProposeStats()
+        q, nq = None, 0
+        if queries is not None:
+            q = np.ascontiguousarray(queries, np.int32).reshape(-1)
+            nq = len(q)
+        gate = float(range) > 0.0
+
+        def call(rng, cap, ij, dist, angle, sigma, zscore, q=q, nq=nq):
+            rc = self.L.spg_graph_propose_candidates(self.h, int(fixed_id), float(search_radius), float(max_angle), int(min_id_gap), int(max_per_vertex),
+                                                     None if q is None else _p(q, C.c_int32), nq, rng, float(z_max),
+                                                     None if ij is None else _p(ij, C.c_int32), None if dist is None else _p(dist, C.c_double),
+                                                     None if angle is None else _p(angle, C.c_double), None if sigma is None else _p(sigma, C.c_double),
+                                                     None if zscore is None else _p(zscore, C.c_double), cap, C.byref(st))
+            check(min(int(rc), 0), self.ctx.h, "proposeCandidates")
+            return int(rc)
+        # the size query runs stage A alone (no fill, no covariance): the gate can only drop pairs of it. Before it, with an
+        # empty query list, the call checks range with the other arguments and returns 0 without touching the backend.
+        if gate:
+            call(float(range), 0, None, None, None, None, None, q=np.zeros(1, np.int32), nq=0)
+        cap = call(0.0 if gate else float(range), 0, None, None, None, None, None)
+        ij, dist, angle = np.zeros((max(cap, 1), 2), np.int32), np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+        sigma, zscore = (np.zeros(max(cap, 1)), np.zeros(max(cap, 1))) if gate else (None, None)
+        n = call(float(range), cap, ij, dist, angle, sigma, zscore) if cap > 0 else 0
+        out = {"ij": ij[:n].copy(), "dist": dist[:n].copy(), "angle": angle[:n].copy()}
+        if gate:
+            out["sigma"], out["zscore"] = sigma[:n].copy(), zscore[:n].copy()
+        self.last_covariance_stats = st.asdict()
+        if stats:
+            out["stats"] = st.asdict()
+        return out
+
     def pruneCandidates(self, edge_idx, k, max_loss=0.0, max_kld=0.0, min_margin=0.0, fixed_id=-1):
         """Greedy choice of up to k of the listed live binary edges (indices into the order of edges()) by conditional
         information loss (include/spg.h: spg_graph_prune_candidates): each round takes the edge whose removal costs the
