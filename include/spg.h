@@ -736,6 +736,44 @@ int64_t spg_graph_propose_candidates(spg_graph *g, int32_t fixed_id, double sear
                                      int32_t *ij, double *dist, double *angle, double *sigma, double *zscore, int64_t cap,
                                      spg_propose_stats *stats);
 
+/* ---- selection of the vertices to remove by spatial redundancy ----------------------------------------------
+ * Which vertices should go: one pose is kept per neighbourhood, so that a place visited a hundred times costs what it
+ * costs when visited once. On the device, at the stored estimates; the graph is not modified and its robust kernel is
+ * ignored. Two distinct live vertices are REDUNDANT iff
+ *   1. |p_a - p_b|_2 <= radius (radius > 0 and finite): rule 1 of spg_graph_propose_candidates, the same arithmetic;
+ *   2. max_angle <= 0, or the rotation angle of X_a^-1 X_b is <= max_angle: rule 2, asked with a the lower id.
+ * There is no adjacency rule, no id-gap rule and no query list. The live vertices are put in a total ORDER: the n_keep
+ * vertices of `keep` first; then the others, by (priority descending, id ascending) when priority is given (one double per
+ * live vertex in ascending-id order; a NaN is SPG_EINVAL with the id in the text), and with priority == NULL by
+ * (mix64((uint64)(uint32)id), id) ascending, mix64 the splitmix64 finaliser (x ^= x >> 30, x *= 0xbf58476d1ce4e5b9,
+ * x ^= x >> 27, x *= 0x94d049bb133111eb, x ^= x >> 31) with all 64 bits kept.
+ * The KEPT set K is the lexicographically first maximal independent set in that order: K starts as the keep list (forced
+ * vertices are kept even when they are redundant with each other); every other vertex, taken in order, joins K iff no
+ * member of K is redundant with it. Everything not in K is REMOVED, and the REPRESENTATIVE of a removed vertex is the kept
+ * vertex redundant with it of smallest (dist, id). So every removed vertex has a kept vertex within radius, no two unforced
+ * kept vertices are redundant, and a second call on the resulting graph removes nothing.
+ * The grid, its table, SPG_PROPOSE_TABLE_BITS and the refusal of poses (not finite: SPG_EINVAL; a cell coordinate that does
+ * not fit: SPG_ECAPACITY; both with the vertex id) are those of spg_graph_propose_candidates with cell edge = radius.
+ * The decision runs in rounds, one kernel launch each, until every vertex is decided; the result does not depend on the
+ * order of the device's atomics: two calls return the same bits. stats.rounds and stats.pairs_tested may differ between
+ * calls. An order that follows the trajectory (priority by id) makes long chains of dependent decisions and so many rounds;
+ * the hashed default keeps them short.
+ * Errors, before the backend is touched and with the offending id in the text (SPG_EINVAL): radius not finite or <= 0,
+ * max_angle = NaN, an unknown or repeated keep id, a NaN priority, an active stepwise marginalisation. SPG_ESTATE without
+ * HIP. Zero or one live vertex returns 0. */
+typedef struct {
+    int32_t n_cells, max_cell_population; int64_t table_slots;   /* as spg_propose_stats */
+    int32_t n_live, n_forced, n_kept, n_removed;
+    int32_t rounds;               /* launches of the decision kernel; diagnostic, may differ between calls */
+    int64_t pairs_tested;         /* distance evaluations of the decision kernel; diagnostic, may differ between calls */
+    double device_seconds;        /* HIP-event time from the grid to the output, the host's reads between the rounds included */
+} spg_removal_stats;
+/* removed (ascending ids), representative, rep_dist: 1 per removed vertex. Returns the number of removed vertices; writes
+ * only when the three are given and cap >= that number. The ids go unchanged into spg_graph_marginalize. */
+int64_t spg_graph_select_removals(spg_graph *g, double radius, double max_angle, const int32_t *keep, int n_keep,
+                                  const double *priority, int32_t *removed, int32_t *representative, double *rep_dist,
+                                  int64_t cap, spg_removal_stats *stats);
+
 /* Removes n live edges of any kind, named by their indices in the order of spg_graph_get_edges (the edge order is
  * canonicalised first, as spg_graph_get_edges does). Survivors keep their relative order. Bridges may be removed: a
  * disconnected graph later shows as SPG_ENOTPD. An index out of range or listed twice and an active stepwise

@@ -678,6 +678,33 @@ public:
         }
         return out;
     }
+    // The vertices to remove by spatial redundancy (include/spg.h: spg_graph_select_removals): one pose is kept per
+    // neighbourhood of `radius` (and of max_angle when > 0), the vertices of `keep` whatever happens, among the others the
+    // higher priority first (one value per live vertex in ascending-id order; empty: a hash of the id). `removed`
+    // (ascending ids) goes unchanged into marginalize(). The graph is not modified.
+    struct RemovalResult {
+        std::vector<int> removed, representative;   // per removed vertex: its id, the kept vertex nearest to it
+        std::vector<double> rep_dist;
+        spg_removal_stats stats;
+    };
+    RemovalResult selectRemovals(double radius, double max_angle = 0.0, const std::vector<int> &keep = {}, const std::vector<double> &priority = {}) {
+        std::vector<int32_t> k(keep.begin(), keep.end());
+        const int32_t *kp = k.empty() ? nullptr : k.data();
+        const double *pp = priority.empty() ? nullptr : priority.data();
+        RemovalResult out{};
+        if (!priority.empty() && (int)priority.size() != spg_graph_num_vertices(_g)) throw std::invalid_argument("selectRemovals: one priority per live vertex");
+        const int64_t cap = spg_graph_select_removals(_g, radius, max_angle, kp, (int)k.size(), pp, nullptr, nullptr, nullptr, 0, &out.stats);
+        check((int)std::min<int64_t>(cap, 0), "selectRemovals");
+        if (cap == 0) return out;
+        std::vector<int32_t> rem((size_t)cap), rep((size_t)cap);
+        out.rep_dist.resize((size_t)cap);
+        const int64_t n = spg_graph_select_removals(_g, radius, max_angle, kp, (int)k.size(), pp, rem.data(), rep.data(), out.rep_dist.data(), cap, &out.stats);
+        check((int)std::min<int64_t>(n, 0), "selectRemovals");
+        out.removed.assign(rem.begin(), rem.begin() + n);
+        out.representative.assign(rep.begin(), rep.begin() + n);
+        out.rep_dist.resize((size_t)n);
+        return out;
+    }
     // Greedy choice of up to k of the listed live binary edges (indices into the order of spg_graph_get_edges) by
     // conditional information loss (include/spg.h: spg_graph_prune_candidates); the graph is not modified.
     struct PruneResult {

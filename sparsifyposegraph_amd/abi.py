@@ -147,6 +147,16 @@ class ProposeStats(C.Structure):
         return d
 
 
+class RemovalStats(C.Structure):
+    """spg_removal_stats (include/spg.h)"""
+    _fields_ = [("n_cells", C.c_int32), ("max_cell_population", C.c_int32), ("table_slots", C.c_int64), ("n_live", C.c_int32),
+                ("n_forced", C.c_int32), ("n_kept", C.c_int32), ("n_removed", C.c_int32), ("rounds", C.c_int32), ("pairs_tested", C.c_int64),
+                ("device_seconds", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # SPG_PRUNE_* (include/spg.h): status of a candidate of spg_graph_prune_candidates
 PRUNE_KEPT, PRUNE_INFO_NOT_PD, PRUNE_BRIDGE, PRUNE_PRUNED = 0, 1, 2, 3
 

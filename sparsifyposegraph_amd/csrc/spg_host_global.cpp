@@ -858,6 +858,79 @@ extern "C" int64_t spg_graph_propose_candidates(spg_graph *g, int32_t fixed_id, 
     return ps.n_gated;
 }
 
+// ================================================================================= selection of removals
+// spg_graph_select_removals: the argument checks, the total order of the live vertices (the keep list, then a sort by
+// priority or by the hashed id), the decision on the device.
+namespace {
+inline uint64_t mix64(uint64_t k) {   // the splitmix64 finaliser, the constants of pp_hash
+    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27; k *= 0x94d049bb133111ebull;
+    k ^= k >> 31;
+    return k;
+}
+}  // namespace
+
+extern "C" int64_t spg_graph_select_removals(spg_graph *g, double radius, double max_angle, const int32_t *keep, int n_keep, const double *priority,
+                                             int32_t *removed, int32_t *representative, double *rep_dist, int64_t cap, spg_removal_stats *stats) {
+    const char *what = "spg_graph_select_removals";
+    if (!g || n_keep < 0 || (n_keep > 0 && !keep)) return SPG_EINVAL;
+    spg_ctx *c = g->ctx;
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(c, SPG_EINVAL, "%s: radius %g must be positive and finite", what, radius);
+    if (std::isnan(max_angle)) return set_err(c, SPG_EINVAL, "%s: max_angle is not a number", what);
+    if (g->active) return set_err(c, SPG_EINVAL, "%s: a stepwise marginalisation is active", what);
+    std::vector<int32_t> order = live_vertices_by_id(g);
+    const int n = (int)order.size();
+    std::vector<int32_t> rank_of(g->vid.size(), -1), ids((size_t)n);
+    std::vector<int64_t> vpo((size_t)n);
+    for (int r = 0; r < n; r++) { rank_of[order[r]] = r; ids[r] = g->vid[order[r]]; vpo[r] = g->vpose[order[r]]; }
+    constexpr uint32_t kNoPlace = ~0u;
+    std::vector<uint32_t> pos((size_t)n, kNoPlace);
+    for (int i = 0; i < n_keep; i++) {
+        const int v = live_index(g, keep[i]);
+        if (v < 0) return fail(c, SPG_EINVAL, "%s: keep %d: vertex %d is not in the graph", what, i, (int)keep[i]);
+        if (pos[rank_of[v]] != kNoPlace) return fail(c, SPG_EINVAL, "%s: keep %d: vertex %d is listed twice", what, i, (int)keep[i]);
+        pos[rank_of[v]] = (uint32_t)i;
+    }
+    if (priority)
+        for (int r = 0; r < n; r++)
+            if (std::isnan(priority[r])) return fail(c, SPG_EINVAL, "%s: the priority of vertex %d is not a number", what, (int)ids[r]);
+    spg_removal_stats rs{};
+    rs.n_live = n; rs.n_forced = n_keep; rs.n_kept = n;
+    if (n < 2) { if (stats) *stats = rs; return 0; }
+    if (!c->is_hip) return set_err(c, SPG_ESTATE, "%s needs the HIP backend", what);
+    int table_bits = -1;
+    if (const char *e = getenv("SPG_PROPOSE_TABLE_BITS")) {
+        table_bits = atoi(e);
+        if (table_bits < 0 || table_bits > 30) return fail(c, SPG_EINVAL, "%s: SPG_PROPOSE_TABLE_BITS=%s is outside 0 .. 30", what, e);
+    }
+    // the unforced ranks in order; rank order is id order, so the rank breaks the ties
+    std::vector<int32_t> rest;
+    for (int r = 0; r < n; r++) if (pos[r] == kNoPlace) rest.push_back(r);
+    if (priority) {
+        std::sort(rest.begin(), rest.end(), [&](int32_t x, int32_t y) { return priority[x] > priority[y] || (priority[x] == priority[y] && x < y); });
+    } else {
+        std::vector<uint64_t> key((size_t)n);
+        for (int r = 0; r < n; r++) key[r] = mix64((uint64_t)(uint32_t)ids[r]);
+        std::sort(rest.begin(), rest.end(), [&](int32_t x, int32_t y) { return key[x] < key[y] || (key[x] == key[y] && x < y); });
+    }
+    for (size_t k = 0; k < rest.size(); k++) pos[rest[k]] = (uint32_t)(n_keep + (int)k);
+    if (int rc = sync_device(g)) return rc;
+    if (int rc = c->be.synchronize(c->be.user)) return rc;
+    c->err[0] = 0;
+    const spg::RemovalsIn in{g->d, n, n_keep, g->dev, vpo.data(), ids.data(), pos.data(), radius, max_angle, table_bits};
+    const bool room = removed && representative && rep_dist;
+    std::vector<int32_t> rem, rep;
+    std::vector<double> rd;
+    if (int rc = spg::hip_select_removals(spg::hip_backend_stream(&c->be), in, room, rem, rep, rd, rs, c->err, sizeof c->err)) return rc;
+    if (stats) *stats = rs;
+    const int64_t count = rs.n_removed;
+    if (!room || cap < count) return count;
+    std::copy(rem.begin(), rem.end(), removed);
+    std::copy(rep.begin(), rep.end(), representative);
+    std::copy(rd.begin(), rd.end(), rep_dist);
+    return count;
+}
+
 // ================================================================================= greedy edge pruning, outlier detection
 namespace {
 // What spg_graph_prune_candidates and spg_graph_detect_outliers share. Candidate i is live edge edge_idx[i] in the order

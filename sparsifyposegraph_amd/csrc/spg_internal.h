@@ -201,6 +201,22 @@ int hip_propose_search(void *stream, const ProposeIn &in, bool fill, std::vector
 int hip_propose_gate(void *stream, const DenseGraphIn &in, const int32_t *va, const int32_t *vb, const int64_t *dst, int32_t ld, int64_t nblk,
                      int64_t blocks_len, const int32_t *ca, const int32_t *cb, const int32_t *slot, int n, double range, double *sigma, double *zscore,
                      spg_cov_solve_stats &stats, char *err, size_t errlen);
+// Selection of the vertices to remove by spatial redundancy (spg_removals.inc: rm_*_kernel on the grid of the proposal;
+// DESIGN 5g-V). The n >= 2 live vertices by rank = ascending id (vpo, id); pos[rank] = the vertex's place in the total order,
+// a permutation of 0 .. n - 1 whose first n_forced places are the keep list. fill = false: the counts (stats) alone.
+// removed (ids, ascending), representative (ids), rep_dist: one entry per removed vertex. Poses and the table are refused
+// as hip_propose_search refuses them.
+struct RemovalsIn {
+    int D, n, n_forced;
+    const void *dev_arena;
+    const int64_t *vpo;
+    const int32_t *id;
+    const uint32_t *pos;
+    double radius, max_angle;
+    int table_bits;
+};
+int hip_select_removals(void *stream, const RemovalsIn &in, bool fill, std::vector<int32_t> &removed, std::vector<int32_t> &representative,
+                        std::vector<double> &rep_dist, spg_removal_stats &stats, char *err, size_t errlen);
 // Per-vertex KLD of the D x D marginals of vertex vo[i] of `other` against vertex vb[i] of `base` (both factorised,
 // one after the other), diff as in the global KLD.
 int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseGraphIn &other, const int32_t *vb, const int32_t *vo, int nk,

@@ -20,6 +20,8 @@
 // to end and walked 64 entries at a time with coalesced reads, so a cell of hundreds of poses costs its wavefront a few
 // sweeps instead of serialising 63 idle lanes behind one, and a sparse neighbourhood (the usual ten partners) is one sweep.
 // Stage B (pp_gate_kernel): the range statistic of every kept pair from the rel / cov of sp_relative_kernel, on the device.
+// The host staging of the grid (pp_stage_grid, pp_sort_cells) is shared with spg_removals.inc, which is included after this
+// file and walks the same cells.
 
 namespace {
 
@@ -452,6 +454,88 @@ __global__ __launch_bounds__(256) void pp_gate_kernel(const double *rel, const d
     zscore[i] = sg > 0.0 ? diff / sg : (diff <= 0.0 ? -__builtin_inf() : __builtin_inf());
 }
 
+// The grid of a fixed-radius search over the n live vertices, staged once for every caller (the proposal, and the
+// selection of removals in spg_removals.inc): the buffers of the table and of the cell-sorted arrays, the keys and their
+// insertion, and the three refusals read back from the flags. `ms`: HIP-event time of the two kernels.
+struct PpGrid {
+    DevBuf dvpo, did, dtkey, dtcnt, dtstart, dtfill, dvkey, dvslot, dsrank, dsx, dsy, dsz, dtaud, dtaui, dflag, dstat;
+    size_t slots = 0;
+    float ms = 0;
+};
+
+// Fills the grid part of `a` (arena, vpo, id, n, radius, the table, the per-rank and the cell-sorted arrays, flag) and runs
+// pp_key_kernel and pp_insert_kernel: nothing searches before every pose is known to have a cell. table_bits < 0:
+// 2^ceil(log2(2 n)) slots. radius_name: what the caller's header calls the cell edge. G.dstat: 6 words for pp_scan_kernel.
+int pp_stage_grid(hipStream_t s, int D, int n, const void *dev_arena, const int64_t *vpo, const int32_t *id, double radius, const char *radius_name,
+                  int table_bits, const char *what, PpGrid &G, PpArgs &a, char *err, size_t errlen) {
+    int bits = table_bits;
+    if (bits < 0) for (bits = 1; (1ll << bits) < 2ll * n; bits++) {}
+    const size_t slots = (size_t)1 << bits;
+    G.slots = slots;
+    int rc = 0;
+    if ((rc = upload(G.dvpo, vpo, (size_t)n, s)) || (rc = upload(G.did, id, (size_t)n, s))) {
+        snprintf(err, errlen, "%s: staging the vertices failed (%d)", what, rc);
+        return rc;
+    }
+    HIPCHK(hipMalloc(&G.dtkey.p, slots * 8));
+    HIPCHK(hipMalloc(&G.dtcnt.p, slots * 4));
+    HIPCHK(hipMalloc(&G.dtstart.p, (slots + 1) * 4));
+    HIPCHK(hipMalloc(&G.dtfill.p, slots * 4));
+    HIPCHK(hipMalloc(&G.dvkey.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&G.dvslot.p, (size_t)n * 4));
+    HIPCHK(hipMalloc(&G.dsrank.p, (size_t)n * 4));
+    HIPCHK(hipMalloc(&G.dsx.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&G.dsy.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&G.dsz.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&G.dtaud.p, (size_t)n * 8));
+    HIPCHK(hipMalloc(&G.dtaui.p, (size_t)n * 4));
+    HIPCHK(hipMalloc(&G.dflag.p, 3 * 4));
+    HIPCHK(hipMalloc(&G.dstat.p, 6 * 8));
+    const int32_t flag0[3] = {0x7fffffff, 0x7fffffff, 0};
+    HIPCHK(hipMemcpy(G.dflag.p, flag0, sizeof flag0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(G.dtkey.p, 0xff, slots * 8, s));
+    HIPCHK(hipMemsetAsync(G.dtcnt.p, 0, slots * 4, s));
+    HIPCHK(hipMemsetAsync(G.dtfill.p, 0, slots * 4, s));
+    a.arena = (const double *)dev_arena; a.vpo = (const int64_t *)G.dvpo.p; a.id = (const int32_t *)G.did.p;
+    a.n = n; a.radius = radius;
+    a.tkey = (unsigned long long *)G.dtkey.p; a.tcnt = (int32_t *)G.dtcnt.p; a.tstart = (int32_t *)G.dtstart.p; a.tfill = (int32_t *)G.dtfill.p;
+    a.mask = (unsigned)(slots - 1);
+    a.vkey = (unsigned long long *)G.dvkey.p; a.vslot = (int32_t *)G.dvslot.p; a.srank = (int32_t *)G.dsrank.p;
+    a.sx = (double *)G.dsx.p; a.sy = (double *)G.dsy.p; a.sz = (double *)G.dsz.p; a.tau_d = (double *)G.dtaud.p; a.tau_id = (int32_t *)G.dtaui.p;
+    a.flag = (int32_t *)G.dflag.p;
+    const dim3 per_vertex((unsigned)((n + 255) / 256));
+    EventTimer t_grid;
+    HIPCHK(t_grid.start(s));
+    by_dim(D, [&](auto d) { hipLaunchKernelGGL((pp_key_kernel<decltype(d)::value>), per_vertex, dim3(256), 0, s, a); });
+    hipLaunchKernelGGL(pp_insert_kernel, per_vertex, dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(t_grid.stop(s));
+    int32_t flag[3];
+    HIPCHK(hipMemcpyAsync(flag, G.dflag.p, sizeof flag, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(t_grid.ms(G.ms));
+    if (flag[0] != 0x7fffffff) {
+        snprintf(err, errlen, "%s: the pose of vertex %d is not finite", what, (int)id[flag[0]]);
+        return SPG_EINVAL;
+    }
+    if (flag[1] != 0x7fffffff) {
+        snprintf(err, errlen, "%s: the cell coordinate of vertex %d does not fit 21 bits at %s %g", what, (int)id[flag[1]], radius_name, radius);
+        return SPG_ECAPACITY;
+    }
+    if (flag[2]) {
+        snprintf(err, errlen, "%s: a cell table of %lld slots is smaller than the number of occupied cells", what, (long long)slots);
+        return SPG_ECAPACITY;
+    }
+    return 0;
+}
+
+// the cells as contiguous runs: the scan over the table's populations (its figures in G.dstat[0 .. 2]) and the scatter
+void pp_sort_cells(hipStream_t s, int D, int n, PpGrid &G, const PpArgs &a) {
+    hipLaunchKernelGGL((pp_scan_kernel<int32_t>), dim3(1), dim3(1024), 0, s, (const int32_t *)G.dtcnt.p, (int)G.slots, (int32_t *)G.dtstart.p,
+                       (long long *)G.dstat.p);
+    by_dim(D, [&](auto d) { hipLaunchKernelGGL((pp_scatter_kernel<decltype(d)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a); });
+}
+
 }  // namespace
 
 namespace spg {
@@ -461,81 +545,32 @@ int hip_propose_search(void *stream, const ProposeIn &in, bool fill, std::vector
     hipStream_t s = (hipStream_t)stream;
     const int n = in.n, D = in.D;
     const char *what = "spg_graph_propose_candidates";
-    int bits = in.table_bits;
-    if (bits < 0) for (bits = 1; (1ll << bits) < 2ll * n; bits++) {}
-    const size_t slots = (size_t)1 << bits;
     int rc = 0;
-    DevBuf dvpo, did, disq, dq, daptr, dadj, dtkey, dtcnt, dtstart, dtfill, dvkey, dvslot, dsrank, dsx, dsy, dsz, dtaud, dtaui, dcnt, doff, doa, dob, dctr,
-        dflag, dstat, dij, ddist, dangle;
-    if ((rc = upload(dvpo, in.vpo, (size_t)n, s)) || (rc = upload(did, in.id, (size_t)n, s)) || (rc = upload(disq, in.isq, (size_t)n, s)) ||
-        (rc = upload(dq, in.qlist, (size_t)in.nq, s)) || (rc = upload(daptr, in.adjptr, (size_t)n + 1, s)) ||
+    PpGrid G;
+    PpArgs a{};
+    DevBuf disq, dq, daptr, dadj, dcnt, doff, doa, dob, dctr, dij, ddist, dangle;
+    if ((rc = upload(disq, in.isq, (size_t)n, s)) || (rc = upload(dq, in.qlist, (size_t)in.nq, s)) || (rc = upload(daptr, in.adjptr, (size_t)n + 1, s)) ||
         (rc = upload(dadj, in.adj, (size_t)in.adjptr[n], s))) {
         snprintf(err, errlen, "%s: staging the vertices failed (%d)", what, rc);
         return rc;
     }
-    HIPCHK(hipMalloc(&dtkey.p, slots * 8));
-    HIPCHK(hipMalloc(&dtcnt.p, slots * 4));
-    HIPCHK(hipMalloc(&dtstart.p, (slots + 1) * 4));
-    HIPCHK(hipMalloc(&dtfill.p, slots * 4));
-    HIPCHK(hipMalloc(&dvkey.p, (size_t)n * 8));
-    HIPCHK(hipMalloc(&dvslot.p, (size_t)n * 4));
-    HIPCHK(hipMalloc(&dsrank.p, (size_t)n * 4));
-    HIPCHK(hipMalloc(&dsx.p, (size_t)n * 8));
-    HIPCHK(hipMalloc(&dsy.p, (size_t)n * 8));
-    HIPCHK(hipMalloc(&dsz.p, (size_t)n * 8));
-    HIPCHK(hipMalloc(&dtaud.p, (size_t)n * 8));
-    HIPCHK(hipMalloc(&dtaui.p, (size_t)n * 4));
     HIPCHK(hipMalloc(&dcnt.p, (size_t)n * 4));
     HIPCHK(hipMalloc(&doff.p, ((size_t)n + 1) * 8));
     HIPCHK(hipMalloc(&dctr.p, 2 * 8));
-    HIPCHK(hipMalloc(&dflag.p, 3 * 4));
-    HIPCHK(hipMalloc(&dstat.p, 6 * 8));
-    const int32_t flag0[3] = {0x7fffffff, 0x7fffffff, 0};
-    HIPCHK(hipMemcpy(dflag.p, flag0, sizeof flag0, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(dtkey.p, 0xff, slots * 8, s));
-    HIPCHK(hipMemsetAsync(dtcnt.p, 0, slots * 4, s));
-    HIPCHK(hipMemsetAsync(dtfill.p, 0, slots * 4, s));
     HIPCHK(hipMemsetAsync(dctr.p, 0, 2 * 8, s));
-    PpArgs a{};
-    a.arena = (const double *)in.dev_arena; a.vpo = (const int64_t *)dvpo.p; a.id = (const int32_t *)did.p; a.isq = (const uint8_t *)disq.p;
-    a.qlist = (const int32_t *)dq.p; a.adjptr = (const int32_t *)daptr.p; a.adj = (const int32_t *)dadj.p;
-    a.n = n; a.radius = in.radius; a.max_angle = in.max_angle; a.min_gap = in.min_id_gap; a.m = in.m;
-    a.tkey = (unsigned long long *)dtkey.p; a.tcnt = (int32_t *)dtcnt.p; a.tstart = (int32_t *)dtstart.p; a.tfill = (int32_t *)dtfill.p;
-    a.mask = (unsigned)(slots - 1);
-    a.vkey = (unsigned long long *)dvkey.p; a.vslot = (int32_t *)dvslot.p; a.srank = (int32_t *)dsrank.p;
-    a.sx = (double *)dsx.p; a.sy = (double *)dsy.p; a.sz = (double *)dsz.p; a.tau_d = (double *)dtaud.p; a.tau_id = (int32_t *)dtaui.p;
-    a.cnt = (int32_t *)dcnt.p; a.off = (const long long *)doff.p; a.ctr = (unsigned long long *)dctr.p; a.flag = (int32_t *)dflag.p;
-    const dim3 per_vertex((unsigned)((n + 255) / 256));
-    EventTimer t_grid, t_search, t_fill;
-    float ms0 = 0, ms1 = 0, ms2 = 0;
-    // the grid: nothing searches before every pose is known to have a cell
-    HIPCHK(t_grid.start(s));
-    by_dim(D, [&](auto d) { hipLaunchKernelGGL((pp_key_kernel<decltype(d)::value>), per_vertex, dim3(256), 0, s, a); });
-    hipLaunchKernelGGL(pp_insert_kernel, per_vertex, dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(t_grid.stop(s));
-    int32_t flag[3];
-    HIPCHK(hipMemcpyAsync(flag, dflag.p, sizeof flag, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(t_grid.ms(ms0));
-    if (flag[0] != 0x7fffffff) {
-        snprintf(err, errlen, "%s: the pose of vertex %d is not finite", what, (int)in.id[flag[0]]);
-        return SPG_EINVAL;
-    }
-    if (flag[1] != 0x7fffffff) {
-        snprintf(err, errlen, "%s: the cell coordinate of vertex %d does not fit 21 bits at search_radius %g", what, (int)in.id[flag[1]], in.radius);
-        return SPG_ECAPACITY;
-    }
-    if (flag[2]) {
-        snprintf(err, errlen, "%s: a cell table of %lld slots is smaller than the number of occupied cells", what, (long long)slots);
-        return SPG_ECAPACITY;
-    }
+    if ((rc = pp_stage_grid(s, D, n, in.dev_arena, in.vpo, in.id, in.radius, "search_radius", in.table_bits, what, G, a, err, errlen))) return rc;
+    const size_t slots = G.slots;
+    a.isq = (const uint8_t *)disq.p; a.qlist = (const int32_t *)dq.p; a.adjptr = (const int32_t *)daptr.p; a.adj = (const int32_t *)dadj.p;
+    a.max_angle = in.max_angle; a.min_gap = in.min_id_gap; a.m = in.m;
+    a.cnt = (int32_t *)dcnt.p; a.off = (const long long *)doff.p; a.ctr = (unsigned long long *)dctr.p;
+    EventTimer t_search, t_fill;
+    float ms1 = 0, ms2 = 0;
+    const float ms0 = G.ms;
     HIPCHK(t_search.start(s));
-    long long *stat = (long long *)dstat.p;
-    hipLaunchKernelGGL((pp_scan_kernel<int32_t>), dim3(1), dim3(1024), 0, s, (const int32_t *)dtcnt.p, (int)slots, (int32_t *)dtstart.p, stat);
+    long long *stat = (long long *)G.dstat.p;
+    pp_sort_cells(s, D, n, G, a);
     by_dim(D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
-        hipLaunchKernelGGL((pp_scatter_kernel<DD>), per_vertex, dim3(256), 0, s, a);
         if (in.nq > 0) hipLaunchKernelGGL((pp_tau_kernel<DD>), dim3((unsigned)in.nq), dim3(64), 0, s, a);
         hipLaunchKernelGGL((pp_pair_kernel<DD, false>), dim3((unsigned)n), dim3(64), 0, s, a);
     });
@@ -544,7 +579,7 @@ int hip_propose_search(void *stream, const ProposeIn &in, bool fill, std::vector
     HIPCHK(t_search.stop(s));
     long long hstat[6];
     unsigned long long hctr[2];
-    HIPCHK(hipMemcpyAsync(hstat, dstat.p, sizeof hstat, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hstat, G.dstat.p, sizeof hstat, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(hctr, dctr.p, sizeof hctr, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(t_search.ms(ms1));

@@ -3200,3 +3200,4 @@ int hip_sparse_marginal_kld(void *stream, const DenseGraphIn &base, const DenseG
 
 #include "spg_compat.inc"
 #include "spg_propose.inc"
+#include "spg_removals.inc"

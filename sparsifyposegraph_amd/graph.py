@@ -561,6 +561,47 @@ class GraphWrapperHIP:
             out["stats"] = st.asdict()
         return out
 
+    def selectRemovals(self, radius, max_angle=0.0, keep=(), priority=None, stats=False):
+        """The vertices to remove by spatial redundancy (include/spg.h: spg_graph_select_removals), on the device, without
+        modifying the graph: one pose is kept per neighbourhood of `radius` (and of `max_angle` when > 0). `keep`: ids
+        that stay whatever happens. `priority` decides who stays among the others, the higher value first, ties to the
+        lower id: None (a hash of the id: no order along the trajectory, the fewest rounds), "oldest" (-id), "newest" (+id),
+        an array with one value per live vertex in ascending-id order, or a dict id -> value over the live ids. Returns
+        (removed, representative, rep_dist): int32[r] ascending ids, ready for marginalize(), for each the kept vertex nearest
+        to it, and the distance; with `stats` also abi.RemovalStats.asdict()."""
+        st = abi.RemovalStats()
+        kp = np.ascontiguousarray(keep, np.int32).reshape(-1)
+        pr = None
+        if priority is not None:
+            ids = np.sort(self.vertices()[0])
+            if isinstance(priority, str):
+                if priority not in ("oldest", "newest"):
+                    raise ValueError('selectRemovals: priority is None, "oldest", "newest", an array or a dict')
+                pr = ids.astype(np.float64) * (-1.0 if priority == "oldest" else 1.0)
+            elif isinstance(priority, dict):
+                missing = [int(i) for i in ids if int(i) not in priority]
+                if missing:
+                    raise ValueError(f"selectRemovals: priority has no value for vertex {missing[0]}")
+                pr = np.array([priority[int(i)] for i in ids], np.float64)
+            else:
+                pr = np.ascontiguousarray(priority, np.float64).reshape(-1)
+                if len(pr) != len(ids):
+                    raise ValueError(f"selectRemovals: priority has {len(pr)} entries for {len(ids)} live vertices")
+
+        def call(cap, rem, rep, rd):
+            rc = self.L.spg_graph_select_removals(self.h, float(radius), float(max_angle), _p(kp, C.c_int32) if len(kp) else None, len(kp),
+                                                  None if pr is None else _p(pr, C.c_double), None if rem is None else _p(rem, C.c_int32),
+                                                  None if rep is None else _p(rep, C.c_int32), None if rd is None else _p(rd, C.c_double), cap,
+                                                  C.byref(st))
+            check(min(int(rc), 0), self.ctx.h, "selectRemovals")
+            return int(rc)
+        # one call: the decision is the whole cost, and no more than every live vertex can be removed
+        cap = max(self.numVertices(), 1)
+        rem, rep, rd = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap)
+        n = call(cap, rem, rep, rd)
+        out = (rem[:n].copy(), rep[:n].copy(), rd[:n].copy())
+        return out + (st.asdict(),) if stats else out
+
     def pruneCandidates(self, edge_idx, k, max_loss=0.0, max_kld=0.0, min_margin=0.0, fixed_id=-1):
         """Greedy choice of up to k of the listed live binary edges (indices into the order of edges()) by conditional
         information loss (include/spg.h: spg_graph_prune_candidates): each round takes the edge whose removal costs the

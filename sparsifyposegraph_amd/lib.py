@@ -87,6 +87,8 @@ SYMBOLS = {
     "spg_ctx_max_clique": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), _i32p, C.c_int, _i32p]),
     "spg_graph_propose_candidates": (C.c_int64, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int, C.c_double,
                                                  C.c_double, _i32p, _f64p, _f64p, _f64p, _f64p, C.c_int64, C.POINTER(abi.ProposeStats)]),
+    "spg_graph_select_removals": (C.c_int64, [C.c_void_p, C.c_double, C.c_double, _i32p, C.c_int, _f64p, _i32p, _i32p, _f64p, C.c_int64,
+                                              C.POINTER(abi.RemovalStats)]),
     "spg_graph_remove_edges": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "spg_ctx_set_linear_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "spg_ctx_set_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),

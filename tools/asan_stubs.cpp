@@ -36,5 +36,6 @@ int hip_sparse_compat(void *, const DenseGraphIn &, const int32_t *, const int32
 int hip_max_clique(void *, int, const uint64_t *, int32_t *, int *, int32_t *, char *, size_t) { return SPG_ENODEV; }
 int hip_propose_search(void *, const ProposeIn &, bool, std::vector<int32_t> &, std::vector<double> &, std::vector<double> &, spg_propose_stats &, char *, size_t) { return SPG_ENODEV; }
 int hip_propose_gate(void *, const DenseGraphIn &, const int32_t *, const int32_t *, const int64_t *, int32_t, int64_t, int64_t, const int32_t *, const int32_t *, const int32_t *, int, double, double *, double *, spg_cov_solve_stats &, char *, size_t) { return SPG_ENODEV; }
+int hip_select_removals(void *, const RemovalsIn &, bool, std::vector<int32_t> &, std::vector<int32_t> &, std::vector<double> &, spg_removal_stats &, char *, size_t) { return SPG_ENODEV; }
 int hip_sparse_marginal_kld(void *, const DenseGraphIn &, const DenseGraphIn &, const int32_t *, const int32_t *, int, const int64_t *, const int64_t *, double *, spg_cov_stats &, char *, size_t) { return SPG_ENODEV; }
 }
